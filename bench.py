@@ -17,10 +17,16 @@ all-reduced over xGMI before each M-step).  value = N / max-over-ranks step
 time.  An extra `weak` line times every rank on its own full N = 2^20 part of
 an N x world batch.
 
-Also reported (same JSON line): the full EM step (E-step + statistics +
-all-reduce + M-step), guided queries/sec (conditional + sample + pdf, Q = 2^20,
-replicas), the roofline of the dominant kernel (HIP events on the kernel's
-stream) and the CPU baseline (the C oracle on the host cores, bounded sample).
+A plain run sets up, warms up, times the --steps headline launches and prints
+the result line, with the roofline of the dominant kernel from the HIP events
+around those same launches.  --dump-outputs DIR also writes a fixed seeded
+sample of the rows of the last timed launch's responsibilities to
+DIR/resp.npy; the inputs are seeded, so two builds can be compared on it.
+
+With --full, also reported (same JSON line): the full EM step (E-step +
+statistics + all-reduce + M-step), guided queries/sec (conditional + sample +
+pdf, Q = 2^20, replicas), the tree, per-leaf EM, Cornell Box and large-K lines
+and the CPU baselines (the C oracle on the host cores, bounded sample).
 """
 import argparse
 import importlib.util
@@ -37,6 +43,8 @@ ROOT = Path(__file__).resolve().parent
 PKG_DIR = ROOT / "sdmm-mitsuba_amd"
 HBM_PEAK = 8.0e12            # B/s, MI355X spec (MI355X_MICROARCH.md)
 FP32_PEAK = 157.3e12         # FLOP/s vector fp32 spec
+DUMP_MAX_BYTES = 32 << 20    # --dump-outputs: size of the sampled responsibility rows
+DUMP_SEED = 0x5D33           # ... and the seed of the row sample
 
 
 def load_pkg():
@@ -393,12 +401,24 @@ def main():
     ap.add_argument("--N", type=int, default=1 << 20)
     ap.add_argument("--Q", type=int, default=1 << 20)
     ap.add_argument("--em-warm", type=int, default=5)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="headline E-step only (profiling)")
-    ap.add_argument("--no-large-k", action="store_true", help="skip the K=256/512 lines")
+    # a plain run times the headline E-step only; --full adds every other
+    # line (EM step, guided queries, tree, Cornell renders, large K, the CPU
+    # baselines), which --no-cpu / --no-extra / --no-large-k then trim
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the extra lines and the CPU baselines (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's responsibilities (a fixed seeded sample of "
+                         "rows, fp32) to DIR/resp.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: headline E-step only (profiling)")
+    ap.add_argument("--no-large-k", action="store_true", help="with --full: skip the K=256/512 lines")
     ap.add_argument("--cpu-sample", type=int, default=1 << 20)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: nproc")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu = args.no_extra = True
 
     import torch
     import torch.distributed as dist
@@ -508,6 +528,18 @@ def main():
     achieved = bytes_per_launch / kern
     log(f"[bench] E-step: {ms_per_step:.3f} ms/step wall, kernel {kern * 1e6:.1f} us, "
         f"{achieved / 1e12:.2f} TB/s")
+
+    if args.dump_outputs and rank == 0:
+        # what the last timed launch wrote: the [n_local][K] responsibilities.
+        # The whole matrix is 512 MB at the defaults, so a fixed seeded sample
+        # of its rows (at most 32 MB, ascending row order) is kept
+        rows = min(n_local, DUMP_MAX_BYTES // (4 * K))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_local, size=rows, replace=False))
+        sample = resp[:n_local][torch.from_numpy(idx).to(dev)].cpu().numpy()
+        dump_dir = Path(args.dump_outputs)
+        dump_dir.mkdir(parents=True, exist_ok=True)
+        np.save(dump_dir / "resp.npy", np.ascontiguousarray(sample, dtype=np.float32))
+        log(f"[bench] wrote {dump_dir / 'resp.npy'}: {rows} of {n_local} rows x {K}")
 
     out = {
         "metric": "EM samples/sec (NxK resp) at K=128, N=2^20",

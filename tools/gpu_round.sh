@@ -17,11 +17,12 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smo
 rc=$?; echo "smoke rc=$rc"; tail -3 "$OUT/smoke_$TAG.log"
 ok $rc || exit $rc
 
-timeout -k 10 300 python bench.py > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
+timeout -k 10 300 python bench.py --full > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
 rc=$?; echo "bench rc=$rc"; cat "$OUT/bench_$TAG.json"
 [ $rc -eq 0 ] || { tail -20 "$OUT/bench_$TAG.err"; exit $rc; }
 
-cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/prof_$TAG" -o run \
-    --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu > "$GRAFT_REPO_ROOT/$OUT/prof_$TAG.log" 2>&1
+REPO=$(pwd)
+cd "${TMPDIR:-/tmp}" && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$REPO/$OUT/prof_$TAG" -o run \
+    --output-format csv -- python3 "$REPO/bench.py" --full --no-cpu > "$REPO/$OUT/prof_$TAG.log" 2>&1
 rc=$?; echo "rocprof rc=$rc"
 exit $rc

@@ -652,6 +652,63 @@ int sdmm_learned4_conditional_device(const sdmm_learned_bsdf4* m, float alpha, i
  * hold cap components. */
 int sdmm_learned4_save_json(const sdmm_learned_bsdf4* m, const char* path);
 int sdmm_learned4_load_json(const char* path, int cap, int* M_out, float* weights, float* means, float* covs);
+/* A learned BSDF over a condition of dimension C: C = 2 is the SDMM4 above,
+ * C = 3 the reference's BSDF::SDMM5 (bsdf.h:316-324) -- Phong on (theta_i,
+ * specWeight = max specular RGB, log max(1, exponent)) (phong.cpp:75-90),
+ * rough dielectric and rough plastic on (theta_i, alpha, eta)
+ * (roughdielectric.cpp:198-211, roughplastic.cpp:212-224).  M <= 8; host arrays
+ *   weights[M]
+ *   means[M][C+3]      the C condition means, then the unit direction
+ *   covs[M][(C+2)^2]   row major over the tangent (c_0 .. c_{C-1}, t1, t2). */
+typedef struct sdmm_learned_bsdf {
+    int C;
+    int M;
+    const float* weights;
+    const float* means;
+    const float* covs;
+} sdmm_learned_bsdf;
+/* getDMM + rotate_to_wo for any of those materials on the host: the condition
+ * is (theta_i = acos(min(1, wi_local[2])), cond_rest[0 .. C-2]).
+ *   keep 1..8, force -1  sdmm::create_conditional_pruned(conditioner, condition,
+ *                        dmm, keep) (roughconductor.cpp:192, roughdielectric.cpp:
+ *                        209, roughplastic.cpp:222)
+ *   keep 1..8, force f   the five-argument create_conditional_pruned(..., keep,
+ *                        f) (phong.cpp:88, f = 1 the diffuse component):
+ *                        component f, when its conditioned weight is > 0, is
+ *                        always kept; f >= M: SDMM_E_INVALID
+ *   keep 0               the unpruned sdmm::create_conditional (blendbsdf.cpp:
+ *                        96): every valid component, in model order
+ * Outputs as sdmm_learned4_conditional (room for 8 lobes when keep is 0); at
+ * C = 2, force -1 they equal its outputs bitwise.  This library's reading of
+ * those sdmm-lib calls (absent from the snapshot): csrc/learned_bsdf.h and
+ * DESIGN.md section 10. */
+int sdmm_learned_conditional(const sdmm_learned_bsdf* m, const float* cond_rest, const float wi_local[3], int keep,
+                             int force, int* n_out, float* weights, float* means, float* covs);
+/* The same for nq queries on the device, each with its own condition (a
+ * wavefront's Phong hits carry different exponents): cond_rest holds C - 1
+ * entries, entry i a device plane of nq values or NULL to broadcast the host
+ * scalar cond_scalar[i].  Outputs device, R = keep (8 when keep is 0) lobes a
+ * query: weights[nq][R], means[nq][R][3], covs[nq][R][4], n_out[nq]; unused
+ * lobes weight 0.  Asynchronous on hip_stream; bitwise the host call's. */
+int sdmm_learned_conditional_device(const sdmm_learned_bsdf* m, const float* const* cond_rest,
+                                    const float* cond_scalar, int64_t nq, const float* const wi_local[3], int keep,
+                                    int force, float* weights, float* means, float* covs, int32_t* n_out,
+                                    void* hip_stream);
+/* sdmm::save_json / load_json of such a model (phong.cpp:102-117): format
+ * "sdmm-amd.sdmm5" with "C" (DESIGN.md section 9); the loader also reads an
+ * "sdmm-amd.sdmm4" file as C = 2.  Load with cap 0 is a size query (*C_out,
+ * *M_out only). */
+int sdmm_learned_save_json(const sdmm_learned_bsdf* m, const char* path);
+int sdmm_learned_load_json(const char* path, int cap, int* C_out, int* M_out, float* weights, float* means,
+                           float* covs);
+/* Phong::sample / eval / pdf (bsdfs/phong.cpp:171-289) on the host, as the
+ * device Li runs them: params = the 8 bsdf_params floats of a kind-3 BSDF,
+ * rho its diffuse reflectance, wi the local incident direction.  With u (2
+ * uniforms): wo is sampled from them (out) and value = eval / pdf (sample's
+ * return value; 0 with pdf 0 for a void sample); u NULL: wo is given and
+ * value = eval (ESolidAngle).  pdf: the solid-angle pdf of wo. */
+int sdmm_bsdf_phong_host(const float* params, const float rho[3], const float wi[3], const float* u, float wo[3],
+                         float value[3], float* pdf);
 typedef struct {
     int n_quads;
     const float* quads;
@@ -677,7 +734,11 @@ typedef struct {
      * (sdmm_proc.cpp:297, :383-409, :764).  Kind 2, rough conductor
      * (bsdfs/roughconductor.cpp; `reflectance` unused): [1..3]
      * specularReflectance, [4] eta, [5] k (a gray conductor), [6] the
-     * Beckmann alpha (isotropic, sampleVisible = false), [7] unused. */
+     * Beckmann alpha (isotropic, sampleVisible = false), [7] unused.  Kind 3,
+     * modified Phong (bsdfs/phong.cpp; its diffuseReflectance in
+     * `reflectance`, both reflectances after configure()'s energy scaling):
+     * [1..3] specularReflectance, [4] exponent, [5] the specular sampling
+     * weight sAvg / (dAvg + sAvg) (phong.cpp:146-148), [6], [7] unused. */
     const float* bsdf_params;
     /* nullable: n_bsdfs entries (appended in round 6) -- a rough conductor's
      * learned BSDF, the material's SDMM4 (roughconductor.cpp:182-194,
@@ -685,6 +746,12 @@ typedef struct {
      * product falls back to the plain conditional (sdmm_proc.cpp:327-392).
      * Only rough conductors read theirs. */
     const struct sdmm_learned_bsdf4* learned_models;
+    /* nullable: n_bsdfs entries (appended after learned_models; the
+     * zero-initialise rule below covers older callers) -- the learned BSDFs
+     * over a C-dimensional condition.  Only Phong BSDFs (kind 3) read theirs:
+     * the material's SDMM5 (phong.cpp:75-90, :102-117), C = 3 and M >= 2 (the
+     * forced diffuse component is index 1); M = 0 (or the array NULL): none. */
+    const struct sdmm_learned_bsdf* learned_models_nd;
 } sdmm_scene_desc;
 /* The descriptor has grown across ABI revisions (bsdf_params was appended):
  * zero-initialise it (`sdmm_scene_desc d = {0};` / `memset`) before filling
@@ -710,7 +777,10 @@ typedef struct {
      * alpha, pruned to 2 lobes -- none or no valid conditional: the plain
      * conditional) then rotate_to_wo(wi) and the shading frame to world,
      * sdmm_proc.cpp:340-355; the component index is then k * max(M, 2) + j
-     * with a conductor in the scene.  0: the plain
+     * with a conductor or a Phong BSDF in the scene.  A Phong BSDF likewise
+     * conditions its SDMM5 (sdmm_scene_desc.learned_models_nd: getDMM on
+     * theta_i, the largest specular channel and log max(1, exponent), pruned
+     * to 2 with the diffuse component 1 forced, phong.cpp:75-90).  0: the plain
      * conditional with bsdf_fraction.  (bsdfOnly never trains, :416, so it
      * is the guided = 0 render; its learned-BSDF branch, :331/:384/:410, is
      * unreachable in the reference.) */

@@ -187,6 +187,15 @@ def lib():
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdmm_learned4_load_json.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
                                               C.c_void_p]
+        L.sdmm_learned_conditional.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                               C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sdmm_learned_conditional_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p * 3,
+                                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p]
+        L.sdmm_learned_save_json.argtypes = [C.c_void_p, C.c_char_p]
+        L.sdmm_learned_load_json.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
+                                             C.c_void_p, C.c_void_p]
+        L.sdmm_bsdf_phong_host.argtypes = [C.c_void_p] * 7
         L.sdmm_stree_publish.argtypes = [C.c_void_p, C.c_void_p]
         L.sdmm_guide_ctx_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.sdmm_guide_ctx_destroy.argtypes = [C.c_void_p]
@@ -256,6 +265,8 @@ EXPORTED_SYMBOLS = [
     "sdmm_pinned_alloc", "sdmm_pinned_free",
     "sdmm_learned4_conditional", "sdmm_learned4_save_json", "sdmm_learned4_load_json",
     "sdmm_learned4_conditional_device",
+    "sdmm_learned_conditional", "sdmm_learned_conditional_device", "sdmm_learned_save_json",
+    "sdmm_learned_load_json", "sdmm_bsdf_phong_host",
 ]
 
 
@@ -1219,7 +1230,7 @@ class _SceneDesc(C.Structure):
                 ("n_bsdfs", C.c_int), ("reflectance", C.c_void_p), ("emitter", C.c_void_p),
                 ("n_emitters", C.c_int), ("radiance", C.c_void_p), ("camera_to_world", C.c_float * 16),
                 ("fov_x_deg", C.c_float), ("near_clip", C.c_float), ("width", C.c_int), ("height", C.c_int),
-                ("bsdf_params", C.c_void_p), ("learned_models", C.c_void_p)]
+                ("bsdf_params", C.c_void_p), ("learned_models", C.c_void_p), ("learned_models_nd", C.c_void_p)]
 
 
 class _Learned4(C.Structure):
@@ -1288,6 +1299,112 @@ class LearnedBSDF:
         _check(lib().sdmm_learned4_conditional(C.byref(self.c), C.c_float(alpha), wl.ctypes.data, keep, C.byref(n),
                                                w.ctypes.data, m.ctypes.data, c.ctypes.data))
         return w[:n.value], m[:n.value], c[:n.value]
+
+
+class _LearnedND(C.Structure):
+    _fields_ = [("C", C.c_int), ("M", C.c_int), ("weights", C.c_void_p), ("means", C.c_void_p),
+                ("covs", C.c_void_p)]
+
+
+class LearnedBSDFND:
+    """A learned BSDF over a condition of dimension C (sdmm_learned_bsdf): C =
+    2 the SDMM4 of LearnedBSDF, C = 3 the reference's BSDF::SDMM5 (bsdf.h:
+    316-324; Phong, rough dielectric, rough plastic) -- weights[M],
+    means[M][C+3] (the condition's mean, then the unit direction),
+    covs[M][(C+2)^2] over the tangent (c_0 .. c_{C-1}, t1, t2)."""
+
+    def __init__(self, weights, means, covs, C=None):
+        self.weights = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        M = self.weights.size
+        if C is None:
+            C = np.asarray(means).size // M - 3
+        self.C = int(C)
+        self.means = np.ascontiguousarray(means, np.float32).reshape(M, self.C + 3)
+        self.covs = np.ascontiguousarray(covs, np.float32).reshape(M, (self.C + 2) ** 2)
+        self.c = _LearnedND(self.C, M, self.weights.ctypes.data, self.means.ctypes.data, self.covs.ctypes.data)
+
+    @property
+    def M(self):
+        return self.weights.size
+
+    def arrays(self):
+        return self.weights, self.means, self.covs
+
+    def save_json(self, path):
+        _check(lib().sdmm_learned_save_json(C.byref(self.c), os.fsencode(path)))
+
+    @classmethod
+    def load_json(cls, path):
+        """An sdmm-amd.sdmm5 file, or an sdmm-amd.sdmm4 one as C = 2."""
+        Cd, M = C.c_int(), C.c_int()
+        _check(lib().sdmm_learned_load_json(os.fsencode(path), 0, C.byref(Cd), C.byref(M), None, None, None))
+        w = np.zeros(M.value, np.float32)
+        mu = np.zeros((M.value, Cd.value + 3), np.float32)
+        cv = np.zeros((M.value, (Cd.value + 2) ** 2), np.float32)
+        _check(lib().sdmm_learned_load_json(os.fsencode(path), M.value, C.byref(Cd), C.byref(M), w.ctypes.data,
+                                            mu.ctypes.data, cv.ctypes.data))
+        return cls(w, mu, cv, Cd.value)
+
+    def conditional(self, cond_rest, wi_local, keep=2, force=-1):
+        """getDMM + rotate_to_wo on the host (sdmm_learned_conditional) at
+        (theta_i from wi_local, *cond_rest): keep 0 unpruned, force the
+        always-kept component (-1: none).  (weights[n], means[n][3],
+        covs[n][4]), n = 0 without a valid conditional."""
+        wl = np.ascontiguousarray(wi_local, np.float32)
+        rest = np.ascontiguousarray(np.atleast_1d(cond_rest), np.float32)
+        if rest.size != self.C - 1:
+            raise SDMMError(f"cond_rest: {self.C - 1} values expected")
+        n = C.c_int()
+        w = np.zeros(8, np.float32)
+        m = np.zeros((8, 3), np.float32)
+        c = np.zeros((8, 4), np.float32)
+        _check(lib().sdmm_learned_conditional(C.byref(self.c), rest.ctypes.data, wl.ctypes.data, keep, force,
+                                              C.byref(n), w.ctypes.data, m.ctypes.data, c.ctypes.data))
+        return w[:n.value], m[:n.value], c[:n.value]
+
+    def conditional_device(self, cond_rest, wl, keep=2, force=-1, stream=None):
+        """sdmm_learned_conditional_device over local directions wl (3 device
+        tensors); cond_rest: C - 1 entries, each a device tensor (one value per
+        query) or a float (broadcast).  (weights (nq, R), means (nq, R, 3),
+        covs (nq, R, 4), n (nq,)) on the device, R = keep (8 when keep is 0)."""
+        import torch
+        cond_rest = list(cond_rest) if isinstance(cond_rest, (list, tuple)) else [cond_rest]
+        if len(cond_rest) != self.C - 1:
+            raise SDMMError(f"cond_rest: {self.C - 1} entries expected")
+        nq = wl[0].numel()
+        dev = wl[0].device
+        R = keep if keep > 0 else 8
+        w = torch.empty((nq, R), device=dev)
+        m = torch.empty((nq, R, 3), device=dev)
+        c = torch.empty((nq, R, 4), device=dev)
+        n = torch.empty(nq, dtype=torch.int32, device=dev)
+        planes = (C.c_void_p * len(cond_rest))(*[x.data_ptr() if hasattr(x, "data_ptr") else None for x in cond_rest])
+        scal = (C.c_float * len(cond_rest))(*[0.0 if hasattr(x, "data_ptr") else float(x) for x in cond_rest])
+        for x in cond_rest:
+            if hasattr(x, "data_ptr") and (x.numel() != nq or x.dtype != torch.float32 or not x.is_contiguous()):
+                raise SDMMError("cond_rest planes: contiguous float32 tensors of one value per query")
+        st = torch.cuda.current_stream(dev) if stream is None else stream
+        _check(lib().sdmm_learned_conditional_device(
+            C.byref(self.c), C.cast(planes, C.c_void_p), C.cast(scal, C.c_void_p), nq,
+            (C.c_void_p * 3)(*[t.data_ptr() for t in wl]), keep, force, w.data_ptr(), m.data_ptr(), c.data_ptr(),
+            n.data_ptr(), C.c_void_p(int(st.cuda_stream) or None)))
+        return w, m, c, n
+
+
+def bsdf_phong_host(params, rho, wi, u=None, wo=None):
+    """Phong::sample (u given: (wo, eval / pdf, pdf)) or eval / pdf of a given
+    wo ((wo, eval, pdf)) on the host (sdmm_bsdf_phong_host), local frame."""
+    params = np.ascontiguousarray(params, np.float32)
+    rho = np.ascontiguousarray(rho, np.float32)
+    wi = np.ascontiguousarray(wi, np.float32)
+    out = np.zeros(3, np.float32) if wo is None else np.array(wo, np.float32)
+    uu = None if u is None else np.ascontiguousarray(u, np.float32)
+    value = np.zeros(3, np.float32)
+    pdf = C.c_float()
+    _check(lib().sdmm_bsdf_phong_host(params.ctypes.data, rho.ctypes.data, wi.ctypes.data,
+                                      None if uu is None else uu.ctypes.data, out.ctypes.data, value.ctypes.data,
+                                      C.cast(C.byref(pdf), C.c_void_p)))
+    return out, value, float(np.float32(pdf.value))
 
 
 class _LiParams(C.Structure):
@@ -1452,6 +1569,15 @@ class Scene:
                 if m is not None:
                     self._model_tab[b] = m.c
             d.learned_models = C.cast(self._model_tab, C.c_void_p)
+        if desc.get("learned_models_nd"):
+            # per BSDF: None or (weights, means, covs) / a LearnedBSDFND
+            self._models_nd = [None if m is None else (m if isinstance(m, LearnedBSDFND) else LearnedBSDFND(*m))
+                               for m in desc["learned_models_nd"]]
+            self._model_nd_tab = (_LearnedND * d.n_bsdfs)()
+            for b, m in enumerate(self._models_nd):
+                if m is not None:
+                    self._model_nd_tab[b] = m.c
+            d.learned_models_nd = C.cast(self._model_nd_tab, C.c_void_p)
         self.width, self.height, self.device = d.width, d.height, device
         h = C.c_void_p()
         _check(lib().sdmm_scene_create(C.byref(d), int(device), C.byref(h)))

@@ -36,6 +36,7 @@ namespace {
 
 constexpr const char* kFormat = "sdmm-amd.asdmm";
 constexpr const char* kFormat4 = "sdmm-amd.sdmm4";   // a learned BSDF (sdmm_learned4_*)
+constexpr const char* kFormat5 = "sdmm-amd.sdmm5";   // one over a C-dimensional condition (sdmm_learned_*)
 constexpr int kVersion = 1;
 constexpr int kScalars = 9;
 
@@ -356,6 +357,7 @@ bool iarr(const Value& o, const char* k, std::vector<int32_t>& out, size_t n) {
     });
 }
 
+// format null: any format string (the caller checks it)
 int read_file(const char* path, std::string& s, Value& root, const char* format = kFormat) {
     FILE* fp = std::fopen(path, "rb");
     if (!fp) return err(SDMM_E_INVALID, std::string("cannot open ") + path);
@@ -370,8 +372,9 @@ int read_file(const char* path, std::string& s, Value& root, const char* format 
     const Value* f = root.get("format");
     const Value* ver = root.get("version");
     long long vv = 0;
-    if (!f || f->kind != Value::Str || f->text != format || !ver || !num_int(*ver, vv) || vv != kVersion)
-        return err(SDMM_E_INVALID, std::string(path) + ": not an " + format + " file (format/version)");
+    if (!f || f->kind != Value::Str || (format && f->text != format) || !ver || !num_int(*ver, vv) || vv != kVersion)
+        return err(SDMM_E_INVALID, std::string(path) + ": not an " + (format ? format : "sdmm-amd") +
+                                       " file (format/version)");
     return SDMM_OK;
 }
 
@@ -598,6 +601,67 @@ int sdmm_learned4_load_json(const char* path, int cap, int* M_out, float* weight
     if (!farr(root, "weights", w, (size_t)M) || !farr(root, "means", mu, 5 * (size_t)M) ||
         !farr(root, "covs", c, 16 * (size_t)M))
         return err(SDMM_E_INVALID, std::string(path) + ": weights / means / covs missing or of the wrong size");
+    *M_out = (int)M;
+    if (cap == 0) return SDMM_OK;
+    if (cap < M) return err(SDMM_E_INVALID, std::string(path) + ": cap smaller than M");
+    std::memcpy(weights, w.data(), sizeof(float) * w.size());
+    std::memcpy(means, mu.data(), sizeof(float) * mu.size());
+    std::memcpy(covs, c.data(), sizeof(float) * c.size());
+    return SDMM_OK;
+}
+
+// A learned BSDF over a C-dimensional condition (sdmm_learned_bsdf):
+// {"format": "sdmm-amd.sdmm5", "version": 1, "C": C, "M": M, "weights": [M],
+// "means": [(C+3) M], "covs": [(C+2)^2 M]}, floats with 9 significant digits;
+// the loader reads an sdmm-amd.sdmm4 file as C = 2.
+int sdmm_learned_save_json(const sdmm_learned_bsdf* m, const char* path) {
+    if (!m || !path || (m->C != 2 && m->C != 3) || m->M < 1 || m->M > 8 || !m->weights || !m->means || !m->covs)
+        return err(SDMM_E_INVALID, "sdmm_learned_save_json: invalid argument");
+    Writer w;
+    w.raw("{\"format\":\"");
+    w.raw(kFormat5);
+    w.raw("\",\"version\":");
+    w.i64(kVersion);
+    w.raw(",\"C\":");
+    w.i64(m->C);
+    w.raw(",\"M\":");
+    w.i64(m->M);
+    w.raw(",");
+    w.farr("weights", m->weights, (size_t)m->M);
+    w.farr("means", m->means, (size_t)(m->C + 3) * (size_t)m->M);
+    w.farr("covs", m->covs, (size_t)((m->C + 2) * (m->C + 2)) * (size_t)m->M);
+    w.close_obj();
+    w.raw("\n");
+    FILE* fp = std::fopen(path, "wb");
+    if (!fp) return err(SDMM_E_INVALID, std::string("cannot write ") + path);
+    const bool ok = std::fwrite(w.s.data(), 1, w.s.size(), fp) == w.s.size();
+    if (std::fclose(fp) != 0 || !ok) return err(SDMM_E_INVALID, std::string("write failed: ") + path);
+    return SDMM_OK;
+}
+
+int sdmm_learned_load_json(const char* path, int cap, int* C_out, int* M_out, float* weights, float* means,
+                           float* covs) {
+    if (!path || !C_out || !M_out || cap < 0 || (cap > 0 && (!weights || !means || !covs)))
+        return err(SDMM_E_INVALID, "sdmm_learned_load_json: invalid argument");
+    std::string text;
+    Value root;
+    int r = read_file(path, text, root, nullptr);
+    if (r) return r;
+    const std::string_view fmt = root.get("format")->text;
+    long long C = 2, M = 0;
+    if (fmt == kFormat5) {
+        const Value* cv = root.get("C");
+        if (!cv || !num_int(*cv, C) || (C != 2 && C != 3)) return err(SDMM_E_INVALID, std::string(path) + ": bad C");
+    } else if (fmt != kFormat4) {
+        return err(SDMM_E_INVALID, std::string(path) + ": not an " + kFormat5 + " or " + kFormat4 + " file");
+    }
+    const Value* mv = root.get("M");
+    if (!mv || !num_int(*mv, M) || M < 1 || M > 8) return err(SDMM_E_INVALID, std::string(path) + ": bad M");
+    std::vector<float> w, mu, c;
+    if (!farr(root, "weights", w, (size_t)M) || !farr(root, "means", mu, (size_t)(C + 3) * (size_t)M) ||
+        !farr(root, "covs", c, (size_t)((C + 2) * (C + 2)) * (size_t)M))
+        return err(SDMM_E_INVALID, std::string(path) + ": weights / means / covs missing or of the wrong size");
+    *C_out = (int)C;
     *M_out = (int)M;
     if (cap == 0) return SDMM_OK;
     if (cap < M) return err(SDMM_E_INVALID, std::string(path) + ": cap smaller than M");

@@ -33,6 +33,7 @@
 #include "sdmm_device.h"
 #include "render_device.h"
 #include "learned_bsdf.h"
+#include "bsdf_phong.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -70,42 +71,8 @@ __device__ __forceinline__ int intersect(const SceneDev& S, const float o[3], co
     return best;
 }
 
-// Frame(n): Mitsuba coordinateSystem (s, t, n)
-__device__ __forceinline__ void frame_of(const float n[3], float s[3], float t[3]) {
-    if (fabsf(n[0]) > fabsf(n[1])) {
-        const float inv = 1.0f / sqrtf(n[0] * n[0] + n[2] * n[2]);
-        t[0] = n[2] * inv; t[1] = 0.0f; t[2] = -n[0] * inv;
-    } else {
-        const float inv = 1.0f / sqrtf(n[1] * n[1] + n[2] * n[2]);
-        t[0] = 0.0f; t[1] = n[2] * inv; t[2] = -n[1] * inv;
-    }
-    s[0] = t[1] * n[2] - t[2] * n[1];
-    s[1] = t[2] * n[0] - t[0] * n[2];
-    s[2] = t[0] * n[1] - t[1] * n[0];
-}
-
-// warp::squareToCosineHemisphere (concentric disk, z guarded to 1e-10)
-__device__ __forceinline__ void cosine_hemisphere(float u0, float u1, float w[3]) {
-    const float r1 = 2.0f * u0 - 1.0f, r2 = 2.0f * u1 - 1.0f;
-    float r, phi;
-    if (r1 == 0.0f && r2 == 0.0f) {
-        r = 0.0f; phi = 0.0f;
-    } else if (r1 * r1 > r2 * r2) {
-        r = r1; phi = (float)(kPi / 4.0) * (r2 / r1);
-    } else {
-        r = r2; phi = (float)(kPi / 2.0) - (r1 / r2) * (float)(kPi / 4.0);
-    }
-    // sin / cos in double, rounded: the float values the CPU restatement
-    // (oracle/sdmm_oracle_li.inc) forms with the C library
-    double sd, cd;
-    sincos((double)phi, &sd, &cd);
-    const float sp = (float)sd, cp = (float)cd;
-    w[0] = r * cp;
-    w[1] = r * sp;
-    float z = sqrtf(fmaxf(0.0f, 1.0f - w[0] * w[0] - w[1] * w[1]));
-    if (z == 0.0f) z = 1e-10f;
-    w[2] = z;
-}
+// Frame(n) (frame_of) and warp::squareToCosineHemisphere (cosine_hemisphere):
+// bsdf_phong.h
 
 // fresnelDielectricExt (libcore/util.cpp:651-681): the unpolarised
 // reflectance at cos(theta_i) for the relative index eta
@@ -292,6 +259,9 @@ li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) 
 // ---------------------------------------------------------------------------
 // Loop head of bounce b for every live path.  guided: the tree holds trained
 // leaves (m_iteration != 0, :311-316); otherwise every query is BSDF only.
+// PHONG: the variant for a scene with Phong BSDFs (the three Li kernels carry
+// Phong's code only there, so the other scenes' kernels keep their registers).
+template <bool PHONG>
 __global__ void __launch_bounds__(256)
 li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int max_depth, int guided,
                 float h, uint64_t seed) {
@@ -367,6 +337,14 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         conductor_sample(wl, bp, rng_uniform(seed, gp, stream, 0), rng_uniform(seed, gp, stream, 1), w, bw, &bpdf);
         Q.bw0[i] = bw[0]; Q.bw1[i] = bw[1]; Q.bw2[i] = bw[2];
         Q.bpdf[i] = bpdf;
+    } else if (PHONG && bp && bp[0] == (float)kBsdfPhong) {
+        // Phong::sample (phong.cpp:232-289); a void sample has weight 0
+        const float* rho = S.refl + 3 * S.quads[q].bsdf;
+        const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};
+        float bw[3], bpdf;
+        phong_sample(wl, bp, rho, rng_uniform(seed, gp, stream, 0), rng_uniform(seed, gp, stream, 1), w, bw, &bpdf);
+        Q.bw0[i] = bw[0]; Q.bw1[i] = bw[1]; Q.bw2[i] = bw[2];
+        Q.bpdf[i] = bpdf;
     } else {
         cosine_hemisphere(rng_uniform(seed, gp, stream, 0), rng_uniform(seed, gp, stream, 1), w);
     }
@@ -386,7 +364,10 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
 // product sampling also the query's shading frame F = [s t n] (Frame(n) of
 // the hit quad), its material (the quad's BSDF: its learned-BSDF table row;
 // diffuse here, so getDMM succeeds for every live path, cosTheta(wi) > 0,
-// bsdfs/diffuse.cpp:86-92) and the BSDF/guide draw.
+// bsdfs/diffuse.cpp:86-92; a rough conductor or a Phong BSDF: the query's own
+// row of the extended table, its learned model conditioned here) and the
+// BSDF/guide draw.
+template <bool PHONG>
 __global__ void __launch_bounds__(256)
 li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict__ count, int product) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -428,6 +409,25 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
             }
             for (int l = kept; l < Q.lM; ++l) Q.lw[row * Q.lM + l] = 0.0f;   // (skipped lobes)
             Q.k_mat[j] = kept > 0 ? (int32_t)row : -1;
+        } else if (PHONG && Q.lw && bp && bp[0] == (float)kBsdfPhong) {
+            // Phong::getDMM (phong.cpp:75-90: the material's SDMM5 conditioned
+            // on (theta_i, max specular channel, log max(1, exponent)), pruned
+            // to 2 with the diffuse component forced) + rotate_to_wo, into the
+            // query's row as for the conductor
+            const float wi[3] = {-P.dx[i], -P.dy[i], -P.dz[i]};
+            const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, QD.n)};
+            const int64_t row = (int64_t)Q.lrow0 + j;
+            const float* lm = S.lmodel_nd ? S.lmodel_nd + (size_t)kLearnedNdStride * QD.bsdf : nullptr;
+            const int M = lm ? (int)lm[1] : 0;
+            int kept = 0;
+            if (M > 0) {
+                const float x[3] = {(float)acos((double)fminf(1.0f, wl[2])), fmaxf(bp[1], fmaxf(bp[2], bp[3])),
+                                    (float)log((double)fmaxf(1.0f, bp[4]))};
+                kept = learned_conditional<3>(lm + 2, M, x, wl, kLearnedKeep, kPhongDiffuseComponent,
+                                              Q.lw + row * Q.lM, Q.lm + row * Q.lM * 3, Q.lc + row * Q.lM * 4);
+            }
+            for (int l = kept; l < Q.lM; ++l) Q.lw[row * Q.lM + l] = 0.0f;   // (skipped lobes)
+            Q.k_mat[j] = kept > 0 ? (int32_t)row : -1;
         }
     }
 }
@@ -439,6 +439,7 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
 // The wavefront marks a query whose BSDF sample was chosen comp == -2 (valid
 // conditional) -- the plain bounce's pdf_mode and the product bounce's
 // choice <= h alike.
+template <bool PHONG>
 __global__ void __launch_bounds__(256)
 li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int rr_depth, float h,
                 uint64_t seed, int product) {
@@ -501,9 +502,9 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
                 weight[ch] = mis_pdf == 0.0f ? 0.0f : f * (1.0f / mis_pdf);
             }
         }
-    } else if (bp && bp[0] == (float)kBsdfConductor) {
-        // rough conductor: the loop head's sample (weight, pdf) or the guide's
-        // direction under eval / pdf (:392-407, :456-507)
+    } else if (bp && (bp[0] == (float)kBsdfConductor || (PHONG && bp[0] == (float)kBsdfPhong))) {
+        // rough conductor, Phong: the loop head's sample (weight, pdf) or the
+        // guide's direction under eval / pdf (:392-407, :456-507)
         const float bw[3] = {Q.bw0[i], Q.bw1[i], Q.bw2[i]};
         if (!valid || comp == -2) {
             wo[0] = Q.b0[i]; wo[1] = Q.b1[i]; wo[2] = Q.b2[i];
@@ -524,7 +525,9 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
             const float wol[3] = {dot3(wo, s), dot3(wo, t), dot3(wo, n)};
             const bool zero = (wo[0] == 0.0f && wo[1] == 0.0f && wo[2] == 0.0f) || !__builtin_isfinite(wol[2]);
             float f[3] = {0.0f, 0.0f, 0.0f};
-            const float bsdf_pdf = zero ? 0.0f : conductor_eval_pdf(wil, wol, bp, f);
+            const float bsdf_pdf = zero ? 0.0f
+                                   : PHONG && bp[0] == (float)kBsdfPhong ? phong_eval_pdf(wil, wol, bp, rho, f)
+                                                                : conductor_eval_pdf(wil, wol, bp, f);
             mis_pdf = bsdf_pdf > 0.0f ? h * bsdf_pdf + (1.0f - h) * Q.pdf[j] : 0.0f;
             for (int ch = 0; ch < 3; ++ch) weight[ch] = mis_pdf == 0.0f ? 0.0f : f[ch] * (1.0f / mis_pdf);
         }
@@ -775,8 +778,8 @@ hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, int64_t path0,
 }
 hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
                            int max_depth, int guided, float h, uint64_t seed, hipStream_t st) {
-    hipLaunchKernelGGL(li_query_kernel, grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce, max_depth, guided,
-                       h, seed);
+    hipLaunchKernelGGL(S.has_phong ? li_query_kernel<true> : li_query_kernel<false>, grid_for(P.P), dim3(256), 0, st,
+                       S, P, Q, path0, bounce, max_depth, guided, h, seed);
     return hipGetLastError();
 }
 size_t li_select_temp_bytes(int64_t n) {
@@ -791,15 +794,15 @@ hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDe
     hipError_t e = hipcub::DeviceSelect::Flagged(temp, temp_bytes, hipcub::CountingInputIterator<int32_t>(0), Q.live,
                                                  Q.idx, count_dev, (int)n, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(li_compact_kernel, grid_for(n), dim3(256), 0, st, S, P, Q, (const int32_t*)count_dev,
-                       product);
+    hipLaunchKernelGGL(S.has_phong ? li_compact_kernel<true> : li_compact_kernel<false>, grid_for(n), dim3(256), 0,
+                       st, S, P, Q, (const int32_t*)count_dev, product);
     return hipGetLastError();
 }
 
 hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
                            int rr_depth, float h, uint64_t seed, int product, hipStream_t st) {
-    hipLaunchKernelGGL(li_shade_kernel, grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce, rr_depth, h, seed,
-                       product);
+    hipLaunchKernelGGL(S.has_phong ? li_shade_kernel<true> : li_shade_kernel<false>, grid_for(P.P), dim3(256), 0, st,
+                       S, P, Q, path0, bounce, rr_depth, h, seed, product);
     return hipGetLastError();
 }
 // getDMM + rotate_to_wo for a batch of local incident directions against one
@@ -838,6 +841,65 @@ hipError_t launch_learned4(const float* rec, int M, float alpha, int64_t nq, con
     for (int i = 0; i < M * kLearnedRec; ++i) m.r[i] = rec[i];
     hipLaunchKernelGGL(learned4_kernel, grid_for(nq), dim3(256), 0, st, m, M, alpha, nq, wl[0], wl[1], wl[2], keep, w,
                        mean, cov, n);
+    return hipGetLastError();
+}
+
+// The same over a condition of dimension C (sdmm_learned_conditional_device):
+// query q's condition is (theta_i, rest[0][q] .. rest[C-2][q]), a null plane
+// broadcasting scal[i]; rows lobes a query (keep, or kLearnedMaxComp when
+// keep is 0: unpruned)
+struct LearnedNdRec {
+    float r[kLearnedMaxComp * learned_rec(kLearnedMaxCond)];
+};
+struct LearnedNdCond {
+    const float* rest[kLearnedMaxCond - 1];
+    float scal[kLearnedMaxCond - 1];
+};
+template <int C>
+__global__ void __launch_bounds__(256)
+learned_nd_kernel(LearnedNdRec model, int M, LearnedNdCond cond, int64_t nq, const float* __restrict__ w0,
+                  const float* __restrict__ w1, const float* __restrict__ w2, int keep, int force, int rows,
+                  float* __restrict__ w, float* __restrict__ mean, float* __restrict__ cov, int32_t* __restrict__ n) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const float wl[3] = {w0[q], w1[q], w2[q]};
+    int kept = 0;
+    if (wl[2] > 0.0f) {
+        float x[C];
+        x[0] = (float)acos((double)fminf(1.0f, wl[2]));
+        for (int i = 0; i < C - 1; ++i) x[1 + i] = cond.rest[i] ? cond.rest[i][q] : cond.scal[i];
+        float lw[kLearnedMaxComp], lm[3 * kLearnedMaxComp], lc[4 * kLearnedMaxComp];
+        kept = learned_conditional<C>(model.r, M, x, wl, keep, force, lw, lm, lc);
+        for (int j = 0; j < kept; ++j) {
+            w[q * rows + j] = lw[j];
+            for (int i = 0; i < 3; ++i) mean[(q * rows + j) * 3 + i] = lm[3 * j + i];
+            for (int i = 0; i < 4; ++i) cov[(q * rows + j) * 4 + i] = lc[4 * j + i];
+        }
+    }
+    for (int j = kept; j < rows; ++j) w[q * rows + j] = 0.0f;
+    n[q] = kept;
+}
+hipError_t launch_learned_nd(int C, const float* rec, int M, const float* const* rest, const float* scal, int64_t nq,
+                             const float* const wl[3], int keep, int force, float* w, float* mean, float* cov,
+                             int32_t* n, hipStream_t st) {
+    if ((C != 2 && C != 3) || M < 0 || M > kLearnedMaxComp || keep < 0 || keep > kLearnedMaxComp || force < -1 ||
+        (force >= 0 && force >= M))
+        return hipErrorInvalidValue;
+    if (nq <= 0) return hipSuccess;
+    LearnedNdRec m{};
+    for (int i = 0; i < M * learned_rec(C); ++i) m.r[i] = rec[i];
+    LearnedNdCond cond{};
+    for (int i = 0; i < C - 1; ++i) {
+        cond.rest[i] = rest ? rest[i] : nullptr;
+        cond.scal[i] = scal ? scal[i] : 0.0f;
+    }
+    const int rows = keep == 0 ? kLearnedMaxComp : keep;
+    if (C == 2)
+        hipLaunchKernelGGL(learned_nd_kernel<2>, grid_for(nq), dim3(256), 0, st, m, M, cond, nq, wl[0], wl[1], wl[2],
+                           keep, force, rows, w, mean, cov, n);
+    else
+        hipLaunchKernelGGL(learned_nd_kernel<3>, grid_for(nq), dim3(256), 0, st, m, M, cond, nq, wl[0], wl[1], wl[2],
+                           keep, force, rows, w, mean, cov, n);
     return hipGetLastError();
 }
 

@@ -16,6 +16,7 @@
 #include "../../include/sdmm_gpu.h"
 #include "render_device.h"
 #include "learned_bsdf.h"
+#include "bsdf_phong.h"
 
 // the scene's derived quad data in plain IEEE float (no FMA contraction), as
 // the CPU restatement of Li forms it (oracle/sdmm_oracle_li.inc)
@@ -35,6 +36,9 @@ hipError_t launch_li_film(const PathsDev& P, int64_t pix0, int64_t npix, int spp
                           float* image_sqr, hipStream_t st);
 hipError_t launch_learned4(const float* rec, int M, float alpha, int64_t nq, const float* const wl[3], int keep,
                            float* w, float* mean, float* cov, int32_t* n, hipStream_t st);
+hipError_t launch_learned_nd(int C, const float* rec, int M, const float* const* rest, const float* scal, int64_t nq,
+                             const float* const wl[3], int keep, int force, float* w, float* mean, float* cov,
+                             int32_t* n, hipStream_t st);
 }  // namespace sdmm
 
 namespace sdmm_detail {
@@ -52,6 +56,7 @@ struct sdmm_scene {
     float* drefl = nullptr;
     float* dbpar = nullptr;
     float* dlmod = nullptr;   // kLearnedStride per BSDF (learned_models), null: none
+    float* dlmod_nd = nullptr;   // kLearnedNdStride per BSDF (learned_models_nd), null: none
     float* drad = nullptr;
     float smin[3] = {0, 0, 0}, snorm = 1.0f, tmin[3] = {0, 0, 0}, tmax[3] = {0, 0, 0};
     // per-render buffers (grown)
@@ -68,10 +73,10 @@ struct sdmm_scene {
     int hfb_cap = 0;
     void* temp = nullptr;
     size_t temp_bytes = 0;
-    // rough conductors with product sampling: the extended learned-BSDF
-    // table -- the caller's B rows re-strided to lM >= kLearnedKeep lobes, then
-    // one row per compact query for the conductor's per-bounce lobes
-    bool has_conductor = false;
+    // rough conductors / Phong BSDFs with product sampling: the extended
+    // learned-BSDF table -- the caller's B rows re-strided to lM >= kLearnedKeep
+    // lobes, then one row per compact query for the material's per-bounce lobes
+    bool per_query_lobes = false;
     void* lt = nullptr;
     size_t lt_bytes = 0;
 };
@@ -151,11 +156,13 @@ int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
     return SDMM_OK;
 }
 
-// The extended learned-BSDF table of a render with rough conductors: rows
+// The extended learned-BSDF table of a render with rough conductors or Phong
+// BSDFs (the materials that condition a learned model per bounce): rows
 // 0 .. B-1 the caller's (device arrays, re-strided to lM = max(M,
 // kLearnedKeep) lobes, the extra lobes weight 0 -- skipped by the product),
-// rows B .. B + cap - 1 the compact queries' own conductor lobes (written by
-// li_compact_kernel).  *tab describes it; s->Q points at the query rows.
+// rows B .. B + cap - 1 the compact queries' own lobes (written by
+// li_compact_kernel; hence the component index k * max(M, 2) + j of such a
+// render).  *tab describes it; s->Q points at the query rows.
 int extend_learned(sdmm_scene* s, const sdmm_bsdf_table& user, int64_t cap, hipStream_t st, sdmm_bsdf_table* tab) {
     const int M = user.M, lM = std::max(M, kLearnedKeep), B = user.B;
     const int64_t rows = (int64_t)B + cap;
@@ -213,7 +220,10 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
                              bp[7] >= 0.0f && bp[7] <= 1.0f) ||
                             (bp[0] == (float)kBsdfConductor && bp[1] >= 0.0f && bp[2] >= 0.0f && bp[3] >= 0.0f &&
                              std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] > 0.0f && std::isfinite(bp[4]) &&
-                             bp[5] >= 0.0f && std::isfinite(bp[5]) && bp[6] > 0.0f && bp[6] <= 2.0f);
+                             bp[5] >= 0.0f && std::isfinite(bp[5]) && bp[6] > 0.0f && bp[6] <= 2.0f) ||
+                            (bp[0] == (float)kBsdfPhong && bp[1] >= 0.0f && bp[2] >= 0.0f && bp[3] >= 0.0f &&
+                             std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] >= 0.0f && std::isfinite(bp[4]) &&
+                             bp[5] >= 0.0f && bp[5] <= 1.0f);
             if (!ok) return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid bsdf_params");
         }
     // learned models: at most kLearnedMaxComp components, finite, unit directions
@@ -235,6 +245,38 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
                 bool ok = r[0] >= 0.0f;
                 for (int i = 0; i < kLearnedRec; ++i) ok = ok && std::isfinite(r[i]);
                 const double n2 = (double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5];
+                if (!ok || std::fabs(n2 - 1.0) > 1e-5)
+                    return fail(SDMM_E_INVALID, "sdmm_scene_create: learned model with a non-finite value, a "
+                                                "negative weight or a non-unit direction");
+            }
+        }
+    }
+    // learned models over a C-dimensional condition: the same checks; a Phong
+    // BSDF's is its SDMM5 with the forced diffuse component 1
+    std::vector<float> lmod_nd;
+    if (d->learned_models_nd) {
+        lmod_nd.assign((size_t)kLearnedNdStride * (size_t)d->n_bsdfs, 0.0f);
+        for (int b = 0; b < d->n_bsdfs; ++b) {
+            const sdmm_learned_bsdf& L = d->learned_models_nd[b];
+            if (L.M == 0) continue;
+            if ((L.C != 2 && L.C != 3) || L.M < 0 || L.M > kLearnedMaxComp || !L.weights || !L.means || !L.covs)
+                return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid learned model (C 2 or 3, 1 <= M <= 8, arrays)");
+            const bool phong = d->bsdf_params && d->bsdf_params[kBsdfParams * b] == (float)kBsdfPhong;
+            if (phong && (L.C != 3 || L.M <= kPhongDiffuseComponent))
+                return fail(SDMM_E_INVALID, "sdmm_scene_create: a Phong BSDF's learned model needs C = 3 and M >= 2");
+            const int R = learned_rec(L.C), nm = L.C + 3, nc = (L.C + 2) * (L.C + 2);
+            float* o = lmod_nd.data() + (size_t)kLearnedNdStride * b;
+            o[0] = (float)L.C;
+            o[1] = (float)L.M;
+            for (int k = 0; k < L.M; ++k) {
+                float* r = o + 2 + R * k;
+                r[0] = L.weights[k];
+                for (int i = 0; i < nm; ++i) r[1 + i] = L.means[nm * k + i];
+                for (int i = 0; i < nc; ++i) r[1 + nm + i] = L.covs[nc * k + i];
+                bool ok = r[0] >= 0.0f;
+                for (int i = 0; i < R; ++i) ok = ok && std::isfinite(r[i]);
+                const float* dir = r + 1 + L.C;
+                const double n2 = (double)dir[0] * dir[0] + (double)dir[1] * dir[1] + (double)dir[2] * dir[2];
                 if (!ok || std::fabs(n2 - 1.0) > 1e-5)
                     return fail(SDMM_E_INVALID, "sdmm_scene_create: learned model with a non-finite value, a "
                                                 "negative weight or a non-unit direction");
@@ -278,7 +320,9 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     // (a conductor some quad uses: the CPU restatement's rule)
     if (d->bsdf_params)
         for (int q = 0; q < d->n_quads; ++q)
-            if (d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfConductor) s->has_conductor = true;
+            if (d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfConductor ||
+                d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfPhong)
+                s->per_query_lobes = true;
     // render() (volpath_sdmm.cpp:375-393): spatialNormalization = the largest
     // extent; the tree box getAABB (:314-332)
     float ext[3], norm = 0.0f;
@@ -301,6 +345,9 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     if (e == hipSuccess && !lmod.empty()) e = hipMalloc(&s->dlmod, sizeof(float) * lmod.size());
     if (e == hipSuccess && !lmod.empty())
         e = hipMemcpy(s->dlmod, lmod.data(), sizeof(float) * lmod.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !lmod_nd.empty()) e = hipMalloc(&s->dlmod_nd, sizeof(float) * lmod_nd.size());
+    if (e == hipSuccess && !lmod_nd.empty())
+        e = hipMemcpy(s->dlmod_nd, lmod_nd.data(), sizeof(float) * lmod_nd.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(s->dquads, qs.data(), sizeof(QuadDev) * qs.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess)
         e = hipMemcpy(s->drefl, d->reflectance, sizeof(float) * 3 * (size_t)d->n_bsdfs, hipMemcpyHostToDevice);
@@ -316,6 +363,10 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     S.refl = s->drefl;
     S.bpar = s->dbpar;
     S.lmodel = s->dlmod;
+    S.lmodel_nd = s->dlmod_nd;
+    if (d->bsdf_params)
+        for (int b = 0; b < d->n_bsdfs; ++b)
+            if (d->bsdf_params[kBsdfParams * b] == (float)kBsdfPhong) S.has_phong = 1;
     S.rad = s->drad;
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 4; ++c) S.cam[4 * r + c] = d->camera_to_world[4 * r + c];
@@ -381,6 +432,90 @@ int sdmm_learned4_conditional_device(const sdmm_learned_bsdf4* m, float alpha, i
     return SDMM_OK;
 }
 
+namespace {
+// the model's records (learned_rec(C) floats each) from the ABI arrays
+bool pack_learned(const sdmm_learned_bsdf* m, float* rec) {
+    if (!m || (m->C != 2 && m->C != 3) || m->M < 0 || m->M > kLearnedMaxComp ||
+        (m->M > 0 && (!m->weights || !m->means || !m->covs)))
+        return false;
+    const int R = learned_rec(m->C), nm = m->C + 3, nc = (m->C + 2) * (m->C + 2);
+    for (int k = 0; k < m->M; ++k) {
+        float* r = rec + R * k;
+        r[0] = m->weights[k];
+        for (int i = 0; i < nm; ++i) r[1 + i] = m->means[nm * k + i];
+        for (int i = 0; i < nc; ++i) r[1 + nm + i] = m->covs[nc * k + i];
+    }
+    return true;
+}
+}  // namespace
+
+int sdmm_learned_conditional(const sdmm_learned_bsdf* m, const float* cond_rest, const float wi_local[3], int keep,
+                             int force, int* n_out, float* weights, float* means, float* covs) {
+    float rec[kLearnedMaxComp * learned_rec(kLearnedMaxCond)];
+    if (!pack_learned(m, rec) || !cond_rest || !wi_local || !n_out || keep < 0 || keep > kLearnedMaxComp ||
+        force < -1 || force >= m->M || !weights || !means || !covs)
+        return fail(SDMM_E_INVALID, "sdmm_learned_conditional: invalid argument (C 2 or 3, M <= 8, 0 <= keep <= 8, "
+                                    "-1 <= force < M)");
+    *n_out = 0;
+    if (m->M == 0 || !(wi_local[2] > 0.0f)) return SDMM_OK;   // getDMM: no model, or cosTheta(wi) <= 0
+    // the device's float environment: denormals flushed (-fgpu-flush-denormals-to-zero)
+    const unsigned csr = _mm_getcsr();
+    _mm_setcsr(csr | 0x8040u);
+    float x[kLearnedMaxCond];
+    x[0] = (float)std::acos((double)std::fmin(1.0f, wi_local[2]));
+    for (int i = 0; i < m->C - 1; ++i) x[1 + i] = cond_rest[i];
+    float w[kLearnedMaxComp], mm[3 * kLearnedMaxComp], cc[4 * kLearnedMaxComp];
+    const int n = m->C == 2 ? learned_conditional<2>(rec, m->M, x, wi_local, keep, force, w, mm, cc)
+                            : learned_conditional<3>(rec, m->M, x, wi_local, keep, force, w, mm, cc);
+    _mm_setcsr(csr);
+    for (int j = 0; j < n; ++j) {
+        weights[j] = w[j];
+        for (int i = 0; i < 3; ++i) means[3 * j + i] = mm[3 * j + i];
+        for (int i = 0; i < 4; ++i) covs[4 * j + i] = cc[4 * j + i];
+    }
+    *n_out = n;
+    return SDMM_OK;
+}
+
+int sdmm_learned_conditional_device(const sdmm_learned_bsdf* m, const float* const* cond_rest,
+                                    const float* cond_scalar, int64_t nq, const float* const wi_local[3], int keep,
+                                    int force, float* weights, float* means, float* covs, int32_t* n_out,
+                                    void* hip_stream) {
+    float rec[kLearnedMaxComp * learned_rec(kLearnedMaxCond)];
+    if (!pack_learned(m, rec) || nq < 0 || keep < 0 || keep > kLearnedMaxComp || force < -1 ||
+        force >= m->M)
+        return fail(SDMM_E_INVALID, "sdmm_learned_conditional_device: invalid argument (C 2 or 3, M <= 8, 0 <= keep "
+                                    "<= 8, -1 <= force < M)");
+    if (nq == 0) return SDMM_OK;
+    if (!wi_local || !wi_local[0] || !wi_local[1] || !wi_local[2] || !weights || !means || !covs || !n_out)
+        return fail(SDMM_E_INVALID, "sdmm_learned_conditional_device: invalid argument");
+    // every condition value comes from a plane or from a scalar
+    for (int i = 0; i < m->C - 1; ++i)
+        if (!(cond_rest && cond_rest[i]) && !cond_scalar)
+            return fail(SDMM_E_INVALID, "sdmm_learned_conditional_device: a condition value with neither a plane "
+                                        "nor a scalar");
+    HIP_TRY(launch_learned_nd(m->C, rec, m->M, cond_rest, cond_scalar, nq, wi_local, keep, force, weights, means,
+                              covs, n_out, (hipStream_t)hip_stream));
+    return SDMM_OK;
+}
+
+int sdmm_bsdf_phong_host(const float* params, const float rho[3], const float wi[3], const float* u, float wo[3],
+                         float value[3], float* pdf) {
+    if (!params || params[0] != (float)kBsdfPhong || !rho || !wi || !wo || !value || !pdf)
+        return fail(SDMM_E_INVALID, "sdmm_bsdf_phong_host: invalid argument (params of a kind-3 BSDF)");
+    const unsigned csr = _mm_getcsr();
+    _mm_setcsr(csr | 0x8040u);
+    if (u) {
+        float o[3] = {0.0f, 0.0f, 1.0f};
+        phong_sample(wi, params, rho, u[0], u[1], o, value, pdf);
+        for (int a = 0; a < 3; ++a) wo[a] = o[a];
+    } else {
+        *pdf = phong_eval_pdf(wi, wo, params, rho, value);
+    }
+    _mm_setcsr(csr);
+    return SDMM_OK;
+}
+
 void sdmm_scene_destroy(sdmm_scene* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -389,6 +524,7 @@ void sdmm_scene_destroy(sdmm_scene* s) {
     if (s->drefl) (void)hipFree(s->drefl);
     if (s->dbpar) (void)hipFree(s->dbpar);
     if (s->dlmod) (void)hipFree(s->dlmod);
+    if (s->dlmod_nd) (void)hipFree(s->dlmod_nd);
     if (s->drad) (void)hipFree(s->drad);
     if (s->buf) (void)hipFree(s->buf);
     if (s->lt) (void)hipFree(s->lt);
@@ -440,7 +576,7 @@ int sdmm_li_render(sdmm_scene* s, sdmm_stree* t, const sdmm_mix* const* node_mix
     s->P.P = P;
     sdmm_bsdf_table ltab{};
     s->Q.lw = s->Q.lm = s->Q.lc = nullptr;
-    if (product && p->guided && s->has_conductor) {
+    if (product && p->guided && s->per_query_lobes) {
         r = extend_learned(s, p->learned_bsdf, s->cap_paths, st, &ltab);
         if (r) return r;
     }

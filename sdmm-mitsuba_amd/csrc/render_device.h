@@ -32,16 +32,19 @@ struct QuadDev {
 };
 
 // Per-BSDF parameters beside the diffuse reflectance (kBsdfParams floats per
-// BSDF): [0] kind (0 diffuse, 1 smooth plastic, 2 rough conductor).
+// BSDF): [0] kind (0 diffuse, 1 smooth plastic, 2 rough conductor, 3 Phong).
 // Plastic: [1..3] specular reflectance, [4] eta = intIOR / extIOR, [5] 1 /
 // eta^2, [6] the internal diffuse Fresnel reflectance fdrInt, [7] the
 // specular sampling weight sAvg / (dAvg + sAvg) (bsdfs/plastic.cpp:159-200).
 // Rough conductor: [1..3] specular reflectance, [4] eta, [5] k (a gray
 // conductor), [6] the Beckmann alpha, [7] unused (bsdfs/roughconductor.cpp).
+// Phong: [1..3] specular reflectance, [4] exponent, [5] the specular sampling
+// weight sAvg / (dAvg + sAvg), [6], [7] unused (bsdfs/phong.cpp:129-156).
 constexpr int kBsdfParams = 8;
 constexpr int kBsdfDiffuse = 0;
 constexpr int kBsdfPlastic = 1;
 constexpr int kBsdfConductor = 2;
+constexpr int kBsdfPhong = 3;
 
 struct SceneDev {
     const QuadDev* quads;
@@ -49,11 +52,13 @@ struct SceneDev {
     const float* refl;    // 3 per BSDF (plastic: its diffuseReflectance)
     const float* bpar;    // kBsdfParams per BSDF; null: every BSDF diffuse
     const float* lmodel;  // kLearnedStride per BSDF: [M, M SDMM4 records] (learned_bsdf.h); null: none
+    const float* lmodel_nd;   // kLearnedNdStride per BSDF: [C, M, M records of learned_rec(C)]; null: none
     const float* rad;     // 3 per emitter
     float cam[12];        // camera-to-world 3x4 (row major)
     float tanx, aspect, near_clip;
     int width, height;
     float smin[3], snorm;
+    int has_phong;        // some BSDF is Phong: the Li kernels' PHONG variants run
 };
 
 struct PathsDev {
@@ -97,9 +102,10 @@ struct QueryDev {
     // sampled lobe delta (1) or smooth (0), its weight (RGB) and pdf
     uint8_t* bdelta;
     float *bw0, *bw1, *bw2, *bpdf;
-    // product with a rough conductor's learned BSDF: compact query j's lobes
-    // (weights, local means, covariances) at row lrow0 + j of the render's
-    // extended learned-BSDF table (lM lobes a row); lw null: no such material
+    // product with a rough conductor's or a Phong BSDF's learned model:
+    // compact query j's lobes (weights, local means, covariances) at row
+    // lrow0 + j of the render's extended learned-BSDF table (lM lobes a row);
+    // lw null: no such material
     float *lw, *lm, *lc;
     int lrow0, lM;
 };

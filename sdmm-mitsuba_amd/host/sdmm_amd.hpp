@@ -752,4 +752,50 @@ inline float mixed_pdf(float heuristicConditionalWeight, float bsdfPdf, float gm
     return heuristicConditionalWeight * bsdfPdf + (1.0f - heuristicConditionalWeight) * gmmPdf;
 }
 
+// A material's learned BSDF over a C-dimensional condition (its SDMM4, C = 2,
+// or SDMM5, C = 3) and its getDMM for a build without sdmm-lib
+// (sdmm_learned_*): Phong keep 2, force 1 (phong.cpp:88); rough conductor /
+// dielectric / plastic keep 2, force -1; Blend keep 0 (unpruned).
+class LearnedBSDF {
+public:
+    LearnedBSDF(int C, std::vector<float> weights, std::vector<float> means, std::vector<float> covs)
+        : w_(std::move(weights)), m_(std::move(means)), c_(std::move(covs)) {
+        if ((C != 2 && C != 3) || w_.empty() || m_.size() != w_.size() * (size_t)(C + 3) ||
+            c_.size() != w_.size() * (size_t)((C + 2) * (C + 2)))
+            throw Error(SDMM_E_INVALID, "LearnedBSDF: array sizes do not match C and M");
+        d_ = sdmm_learned_bsdf{C, (int)w_.size(), w_.data(), m_.data(), c_.data()};
+    }
+    LearnedBSDF(const LearnedBSDF&) = delete;
+    LearnedBSDF& operator=(const LearnedBSDF&) = delete;
+    static std::unique_ptr<LearnedBSDF> load(const std::string& path) {
+        int C = 0, M = 0;
+        check(sdmm_learned_load_json(path.c_str(), 0, &C, &M, nullptr, nullptr, nullptr), "sdmm_learned_load_json");
+        std::vector<float> w((size_t)M), m((size_t)M * (size_t)(C + 3)), c((size_t)M * (size_t)((C + 2) * (C + 2)));
+        check(sdmm_learned_load_json(path.c_str(), M, &C, &M, w.data(), m.data(), c.data()), "sdmm_learned_load_json");
+        return std::make_unique<LearnedBSDF>(C, std::move(w), std::move(m), std::move(c));
+    }
+    void save(const std::string& path) const { check(sdmm_learned_save_json(&d_, path.c_str()), "sdmm_learned_save_json"); }
+    const sdmm_learned_bsdf& desc() const { return d_; }
+    // lobes (<= 8) for the local incident direction; returns their number (0: getDMM fails)
+    int conditional(const float* cond_rest, const float wi_local[3], int keep, int force, float* weights,
+                    float* means, float* covs) const {
+        int n = 0;
+        check(sdmm_learned_conditional(&d_, cond_rest, wi_local, keep, force, &n, weights, means, covs),
+              "sdmm_learned_conditional");
+        return n;
+    }
+    // a wavefront of getDMM calls in one launch (device planes; see sdmm_gpu.h)
+    void conditional_device(const float* const* cond_rest, const float* cond_scalar, int64_t nq,
+                            const float* const wi_local[3], int keep, int force, float* weights, float* means,
+                            float* covs, int32_t* n_out, void* hip_stream) const {
+        check(sdmm_learned_conditional_device(&d_, cond_rest, cond_scalar, nq, wi_local, keep, force, weights, means,
+                                              covs, n_out, hip_stream),
+              "sdmm_learned_conditional_device");
+    }
+
+private:
+    std::vector<float> w_, m_, c_;
+    sdmm_learned_bsdf d_{};
+};
+
 }  // namespace sdmm_amd

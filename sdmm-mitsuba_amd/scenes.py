@@ -154,6 +154,28 @@ def conductor_params(specular_rgb=(1.0, 1.0, 1.0), eta=1.2, k=7.0, alpha=0.2):
     return np.array([2.0, *specular_rgb, eta, k, alpha, 0.0], np.float32)
 
 
+def phong_params(diffuse_rgb, specular_rgb=(0.2, 0.2, 0.2), exponent=30.0):
+    """(the 8 bsdf_params floats of a Phong BSDF, its diffuse reflectance)
+    after Phong::configure() (bsdfs/phong.cpp:127-156; include/sdmm_gpu.h
+    sdmm_scene_desc): kind 3, specularReflectance, the exponent and the
+    specular sampling weight sAvg / (dAvg + sAvg) from the luminances; both
+    reflectances scaled by 0.99 / max when their channel-wise sum exceeds 1
+    (ensureEnergyConservation, librender/bsdf.cpp:115-146)."""
+    f32 = np.float32
+    d = np.asarray(diffuse_rgb, f32)
+    sp = np.asarray(specular_rgb, f32)
+    actual_max = f32((d + sp).max())
+    if actual_max > 1.0:
+        scale = f32(f32(0.99) * f32(f32(1.0) / actual_max))
+        d, sp = (d * scale).astype(f32), (sp * scale).astype(f32)
+
+    def lum(c):
+        return f32(f32(f32(c[0] * f32(0.212671)) + f32(c[1] * f32(0.715160))) + f32(c[2] * f32(0.072169)))
+    d_avg, s_avg = lum(d), lum(sp)
+    ssw = f32(s_avg / f32(d_avg + s_avg))
+    return np.array([3.0, *sp, exponent, ssw, 0.0, 0.0], f32), d
+
+
 LEARNED_CONDUCTOR = Path(__file__).resolve().parent / "data" / "conductor_beckmann_4c.sdmm4.json"
 
 
@@ -169,7 +191,26 @@ def load_learned(path=LEARNED_CONDUCTOR):
             np.asarray(doc["covs"], np.float32).reshape(M, 16))
 
 
-def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, learned=LEARNED_CONDUCTOR):
+LEARNED_PHONG = Path(__file__).resolve().parent / "data" / "phong_4c.sdmm5.json"
+
+
+def load_learned_nd(path=LEARNED_PHONG):
+    """A learned BSDF over a C-dimensional condition (sdmm-amd.sdmm5 JSON,
+    include/sdmm_gpu.h sdmm_learned_load_json; an sdmm-amd.sdmm4 file is C =
+    2) as (weights[M], means[M][C+3], covs[M][(C+2)^2]) float32."""
+    doc = json.loads(Path(path).read_text())
+    fmt = doc.get("format")
+    if fmt not in ("sdmm-amd.sdmm5", "sdmm-amd.sdmm4") or doc.get("version") != 1:
+        raise ValueError(f"{path}: not an sdmm-amd.sdmm5 file")
+    C = int(doc["C"]) if fmt == "sdmm-amd.sdmm5" else 2
+    M = int(doc["M"])
+    return (np.asarray(doc["weights"], np.float32).reshape(M),
+            np.asarray(doc["means"], np.float32).reshape(M, C + 3),
+            np.asarray(doc["covs"], np.float32).reshape(M, (C + 2) ** 2))
+
+
+def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, learned=LEARNED_CONDUCTOR, phong=(),
+                phong_learned=LEARNED_PHONG, phong_specular=(0.4, 0.4, 0.4), phong_exponent=30.0):
     """sdmm_scene_desc fields for the Cornell Box (numpy arrays).  plastic:
     names of BSDFs (e.g. "TallBox", "ShortBox", "Floor") rendered as smooth
     plastic over their diffuse reflectance (a delta specular lobe beside a
@@ -178,7 +219,11 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
     `roughconductor` materials) tinted by their reflectance, Beckmann alpha,
     each with the learned BSDF `learned` (an sdmm4 file; None: no learned
     model, so product sampling falls back to the plain conditional there) --
-    the synthetic stand-in of tools/make_learned_conductor.py by default."""
+    the synthetic stand-in of tools/make_learned_conductor.py by default.
+    phong: names rendered as Phong BSDFs (the Kitchen's most common learned
+    material) over their diffuse reflectance with phong_specular /
+    phong_exponent, each with the learned SDMM5 `phong_learned` (None: no
+    model) -- the stand-in of tools/make_learned_phong.py by default."""
     names = list(_BSDFS)
     quads, bsdf, flip, emitter = [], [], [], []
     for m, name, fl in _RECTS:
@@ -192,25 +237,33 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
     bsdf.append(names.index("Light")); flip.append(0); emitter.append(0)
     cam = np.array([float(x) for x in _CAMERA.split()], np.float32)
     extra = {}
-    if plastic or conductor:
-        unknown = (set(plastic) | set(conductor)) - set(names)
-        if unknown or set(plastic) & set(conductor):
-            raise ValueError(f"unknown or doubly assigned BSDFs {sorted(unknown | (set(plastic) & set(conductor)))}")
+    refl = {n: _BSDFS[n] for n in names}
+    if plastic or conductor or phong:
+        kinds = [set(plastic), set(conductor), set(phong)]
+        unknown = set().union(*kinds) - set(names)
+        twice = (kinds[0] & kinds[1]) | (kinds[0] & kinds[2]) | (kinds[1] & kinds[2])
+        if unknown or twice:
+            raise ValueError(f"unknown or doubly assigned BSDFs {sorted(unknown | twice)}")
         bp = np.zeros((len(names), 8), np.float32)
         for i, nm in enumerate(names):
             if nm in plastic:
                 bp[i] = plastic_params(_BSDFS[nm])
             elif nm in conductor:
                 bp[i] = conductor_params(tuple(min(1.0, 1.25 * c) for c in _BSDFS[nm]), alpha=alpha)
+            elif nm in phong:
+                bp[i], refl[nm] = phong_params(_BSDFS[nm], phong_specular, phong_exponent)
         extra["bsdf_params"] = bp.reshape(-1)
         if conductor and learned is not None:
             model = load_learned(learned)
             extra["learned_models"] = [model if nm in conductor else None for nm in names]
+        if phong and phong_learned is not None:
+            model = load_learned_nd(phong_learned)
+            extra["learned_models_nd"] = [model if nm in phong else None for nm in names]
     return {**extra,
         "quads": np.asarray(quads, np.float32).reshape(-1),
         "flip_normals": np.asarray(flip, np.int32),
         "bsdf": np.asarray(bsdf, np.int32),
-        "reflectance": np.asarray([_BSDFS[n] for n in names], np.float32).reshape(-1),
+        "reflectance": np.asarray([refl[n] for n in names], np.float32).reshape(-1),
         "emitter": np.asarray(emitter, np.int32),
         "radiance": spectrum_to_rgb(_LIGHT_SPD).astype(np.float32),
         "camera_to_world": cam,

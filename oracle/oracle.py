@@ -497,14 +497,93 @@ def learned4_conditional(model, alpha, wl, keep=2):
     return ow[:n], om[:n], oc[:n]
 
 
+ND_MAXC = 3
+
+
+def nd_rec(C_):
+    """Floats of one record of a model over a C-dimensional condition: weight,
+    mean (C + 3), covariance ((C + 2)^2)."""
+    return 1 + (C_ + 3) + (C_ + 2) ** 2
+
+
+ND_STRIDE = 2 + L4_MAX * nd_rec(ND_MAXC)
+
+
+def _nd_records(model):
+    w, mu, cv = (np.asarray(x, np.float32) for x in model)
+    M = len(w)
+    Cd = mu.size // M - 3
+    rec = np.concatenate([w.reshape(M, 1), mu.reshape(M, Cd + 3), cv.reshape(M, (Cd + 2) ** 2)], axis=1)
+    return Cd, M, np.ascontiguousarray(rec, np.float32)
+
+
+def pack_learned_models_nd(models, n_bsdfs):
+    """desc["learned_models_nd"] (per BSDF None or (weights[M], means[M][C+3],
+    covs[M][(C+2)^2])) as the oracle's packed table: ND_STRIDE floats per BSDF,
+    [C, M, M records of nd_rec(C) floats]; None when there are none."""
+    if not models:
+        return None
+    out = np.zeros((n_bsdfs, ND_STRIDE), np.float32)
+    for b, m in enumerate(models):
+        if m is None:
+            continue
+        Cd, M, rec = _nd_records(m)
+        assert 2 <= Cd <= ND_MAXC and M <= L4_MAX
+        out[b, 0], out[b, 1] = Cd, M
+        out[b, 2:2 + rec.size] = rec.reshape(-1)
+    return np.ascontiguousarray(out)
+
+
+def learned_nd_conditional(model, rest, wl, keep=2, force=-1):
+    """or_learned_nd_conditional: the lobes (weights, local means, 2x2
+    covariances) of one model over a C-dimensional condition at (theta_i of
+    the local incident direction wl, *rest); keep 0: unpruned, force: the
+    component that is always kept (-1, or one that is not valid: none)."""
+    Cd, M, rec = _nd_records(model)
+    rest = np.ascontiguousarray(np.atleast_1d(rest), np.float32)
+    assert rest.size == Cd - 1
+    ow = np.zeros(L4_MAX, np.float32)
+    om = np.zeros((L4_MAX, 3), np.float32)
+    oc = np.zeros((L4_MAX, 4), np.float32)
+    wl = np.ascontiguousarray(wl, np.float32)
+    f = lib().or_learned_nd_conditional
+    f.restype = C.c_int
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    n = f(vp(rec), C.c_int(Cd), C.c_int(M), vp(rest), vp(wl), C.c_int(keep), C.c_int(force), vp(ow), vp(om), vp(oc))
+    return ow[:n], om[:n], oc[:n]
+
+
+def bsdf_phong(params, rho, wi, u=None, wo=None):
+    """or_bsdf_phong, local frame: Phong::sample (u given: (wo, eval / pdf,
+    pdf)) or eval and pdf at a given wo ((wo, eval, pdf))."""
+    params = np.ascontiguousarray(params, np.float32)
+    rho = np.ascontiguousarray(rho, np.float32)
+    wi = np.ascontiguousarray(wi, np.float32)
+    assert (u is None) != (wo is None)
+    out = np.zeros(3, np.float32) if wo is None else np.array(wo, np.float32)
+    uu = None if u is None else np.ascontiguousarray(u, np.float32)
+    value = np.zeros(3, np.float32)
+    pdf = np.zeros(1, np.float32)
+    f = lib().or_bsdf_phong
+    f.restype = None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    if uu is not None:
+        f(vp(params), vp(rho), vp(wi), vp(uu), None, vp(out), vp(value), vp(pdf), None, None)
+    else:
+        f(vp(params), vp(rho), vp(wi), None, vp(out), None, None, None, vp(value), vp(pdf))
+    return out, value, float(pdf[0])
+
+
 def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_depth=10, rr_depth=10, h=0.5,
               V=9, seed=0, pixels=None, learned=None, threads=1):
     """SDMMRenderer::Li restated on the CPU (sdmm_oracle_li.inc) for a
     scene description (scenes.cornell_box() fields), the tree (aabb (n, 6),
     child (n, 2)) and per-node oracle Mixtures (None: no trained context).
     learned: (weights (B, M), means (B, M, 3), covs (B, M, 4), diffuse (B,))
-    for sampleProduct.  Returns dict image (3, H, W), image_sqr, rec
-    (16, V, P), nv (P,), comps (bounces, P)."""
+    for sampleProduct.  desc["learned_models"] / desc["learned_models_nd"]:
+    the conductors' SDMM4s / the Phong BSDFs' SDMM5s.  Returns dict image
+    (3, H, W), image_sqr, rec (16, V, P), nv (P,), comps (bounces, P),
+    hit_bsdf (bounces, P): the BSDF each live bounce scattered at (-1: none)."""
     W, H = int(desc["width"]), int(desc["height"])
     lo, hi = (0, W * H) if pixels is None else pixels
     P = (hi - lo) * spp
@@ -530,6 +609,7 @@ def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_d
     nv = np.zeros(P, np.int32)
     bounces = max_depth - 1 if max_depth > 0 else V
     comps = np.full((bounces, P), -9, np.int32)
+    hit_bsdf = np.full((bounces, P), -1, np.int32)
     if learned is not None:
         bw, bm, bc, bd = f32(learned[0]), f32(learned[1]), f32(learned[2]), np.ascontiguousarray(learned[3], np.uint8)
         M = bw.shape[1]
@@ -542,12 +622,14 @@ def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_d
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     bpar = f32(desc["bsdf_params"]) if "bsdf_params" in desc else None
     lmod = pack_learned_models(desc.get("learned_models"), len(refl) // 3)
+    lmod_nd = pack_learned_models_nd(desc.get("learned_models_nd"), len(refl) // 3)
     rc = f(vp(quads), vp(flip), vp(bsdf), C.c_int(len(bsdf)), vp(refl), vp(bpar) if bpar is not None else None,
            vp(em), vp(rad), vp(cam),
            C.c_float(desc["fov_x_deg"]), C.c_float(desc["near_clip"]), C.c_int(W), C.c_int(H), vp(mn), vp(mx),
            vp(ch), tab, C.c_int(int(guided)), C.c_int(spp), C.c_int(max_depth), C.c_int(rr_depth), C.c_float(h),
            C.c_int(V), C.c_uint64(seed), C.c_int64(lo), C.c_int64(hi), C.c_int(1 if learned is not None else 0),
            vp(bw), vp(bm), vp(bc), vp(bd), C.c_int(M), C.c_int(kmax), vp(image), vp(image_sqr), vp(rec), vp(nv),
-           vp(comps), C.c_int(threads), vp(lmod) if lmod is not None else None)
+           vp(comps), C.c_int(threads), vp(lmod) if lmod is not None else None,
+           vp(lmod_nd) if lmod_nd is not None else None, vp(hit_bsdf))
     assert rc == 0, "or_li_render failed"
-    return {"image": image, "image_sqr": image_sqr, "rec": rec, "nv": nv, "comps": comps}
+    return {"image": image, "image_sqr": image_sqr, "rec": rec, "nv": nv, "comps": comps, "hit_bsdf": hit_bsdf}

@@ -37,6 +37,22 @@
  *              the shading frame to world (:340-355), the product's
  *              non-diffuse branch; BSDF samples and the guide's direction
  *              under eval / pdf as for any smooth BSDF
+ *   :327-355   a Phong BSDF (bsdf kind 3; bsdfs/phong.cpp:171-289, both
+ *              components): li_phong_sample at the loop head, the guide's
+ *              direction under li_phong_eval_pdf, handled like the conductor
+ *              in every other respect (no delta lobe, every bounce cacheable);
+ *              in a product bounce its learned SDMM5 (getDMM, phong.cpp:75-90)
+ *              conditioned on (theta_i, max specular channel, log max(1,
+ *              exponent)), pruned to 2 with component 1 (the diffuse one)
+ *              forced -- li_learned_nd_conditional -- then rotate_to_wo
+ *
+ * The product's lobes per table row, lM: the device gives every compact query
+ * a row of its own with max(M, 2) lobes as soon as some quad of the scene has
+ * a rough-conductor or a Phong BSDF -- whether or not that BSDF carries a
+ * learned model (sdmm_scene_create sets per_query_lobes from the BSDF kinds
+ * alone; extend_learned re-strides the caller's rows, the extra lobes weight
+ * 0) -- and M lobes otherwise.  or_li_render follows that rule, so the
+ * component indices k * lM + j agree.
  *
  * Scene conventions (Mitsuba): diffuse BSDFs sample the cosine hemisphere
  * (warp::squareToCosineHemisphere, concentric map) in Frame(n) (Mitsuba's
@@ -70,6 +86,7 @@ typedef struct {
     const float* refl;
     const float* bpar;   /* 8 per BSDF (include/sdmm_gpu.h bsdf_params); NULL: all diffuse */
     const float* lmodel; /* LI_L4_STRIDE per BSDF: [M, M SDMM4 records]; NULL: no learned models */
+    const float* lmodel_nd; /* LI_ND_STRIDE per BSDF: [C, M, M records of LI_ND_REC(C)]; NULL: none */
     const float* rad;
     float cam[12];
     float tanx, aspect, near_clip;
@@ -285,6 +302,55 @@ static void li_l4_cong(float b00, float b01, float b10, float b11, float s00, fl
     c[1] = t00 * b10 + t01 * b11;
     c[2] = t10 * b10 + t11 * b11;
 }
+/* rotate_to_wo's rotation about the normal: cos / sin of wl's azimuth (1, 0 at the pole) */
+static void li_l4_azimuth(const float wl[3], float* cr, float* sr) {
+    const float sp2 = wl[0] * wl[0] + wl[1] * wl[1];
+    *cr = 1.0f;
+    *sr = 0.0f;
+    if (sp2 > 0.0f) {
+        const float rs = 1.0f / sqrtf(sp2);
+        *cr = wl[0] * rs;
+        *sr = wl[1] * rs;
+    }
+}
+/* One conditioned component as a lobe (shared by the SDMM4 and the N-D
+ * conditional): mean' = exp_{mu}(a0, a1), the covariance sc (s00, s01, s11 in
+ * Coordinates(mu)) transported there, then rotate_to_wo by (cr, sr): mean[3],
+ * cov[4] in Coordinates(mean). */
+static void li_l4_lobe(const float* mu_d, float a0, float a1, const float sc[3], float cr, float sr, float* mean,
+                       float* cov) {
+    const float mu[3] = {mu_d[0], mu_d[1], mu_d[2]};
+    float tm[9], td[9], tr[9], c1[3], c2[3];
+    or_coordinates(mu, tm);
+    float d[3] = {mu[0], mu[1], mu[2]};
+    float e1[3] = {tm[0], tm[1], tm[2]}, e2[3] = {tm[3], tm[4], tm[5]};
+    const float len2 = a0 * a0 + a1 * a1;
+    if (len2 > 0.0f) {
+        /* the geodesic from mu along u = shift / |shift|; mu's axes parallel-transported along it */
+        const float len = sqrtf(len2);
+        const float sn = (float)sin((double)len), cs = (float)cos((double)len);
+        const float u0 = a0 / len, u1 = a1 / len;
+        float u[3];
+        for (int i = 0; i < 3; ++i) u[i] = u0 * tm[i] + u1 * tm[3 + i];
+        for (int i = 0; i < 3; ++i) d[i] = cs * mu[i] + sn * u[i];
+        for (int i = 0; i < 3; ++i) {
+            const float g = (cs - 1.0f) * u[i] - sn * mu[i];
+            e1[i] = tm[i] + u0 * g;
+            e2[i] = tm[3 + i] + u1 * g;
+        }
+    }
+    const float rn = 1.0f / sqrtf(li_dot3(d, d));
+    for (int i = 0; i < 3; ++i) d[i] = d[i] * rn;
+    or_coordinates(d, td);
+    li_l4_cong(li_dot3(td, e1), li_dot3(td, e2), li_dot3(td + 3, e1), li_dot3(td + 3, e2), sc[0], sc[1], sc[2], c1);
+    const float m[3] = {cr * d[0] - sr * d[1], sr * d[0] + cr * d[1], d[2]};
+    or_coordinates(m, tr);
+    const float r1[3] = {cr * td[0] - sr * td[1], sr * td[0] + cr * td[1], td[2]};
+    const float r2[3] = {cr * td[3] - sr * td[4], sr * td[3] + cr * td[4], td[5]};
+    li_l4_cong(li_dot3(tr, r1), li_dot3(tr, r2), li_dot3(tr + 3, r1), li_dot3(tr + 3, r2), c1[0], c1[1], c1[2], c2);
+    mean[0] = m[0]; mean[1] = m[1]; mean[2] = m[2];
+    cov[0] = c2[0]; cov[1] = c2[1]; cov[2] = c2[1]; cov[3] = c2[2];
+}
 static int li_learned_conditional(const float* rec, int M, float theta, float alpha, const float wl[3], int keep,
                                   float* w, float* mean, float* cov) {
     const float two_pi = 6.28318530717958647692f;
@@ -337,51 +403,12 @@ static int li_learned_conditional(const float* rec, int M, float theta, float al
         sum += pw[best];
     }
     if (n == 0 || !(sum > 0.0f) || !(sum < INFINITY)) return 0;
-    const float sp2 = wl[0] * wl[0] + wl[1] * wl[1];
-    float cr = 1.0f, sr = 0.0f;
-    if (sp2 > 0.0f) {
-        const float rs = 1.0f / sqrtf(sp2);
-        cr = wl[0] * rs;
-        sr = wl[1] * rs;
-    }
+    float cr, sr;
+    li_l4_azimuth(wl, &cr, &sr);
     for (int j = 0; j < n; ++j) {
         const int k = sel[j];
-        const float* p = rec + LI_L4_REC * k;
-        const float mu[3] = {p[3], p[4], p[5]};
-        float tm[9], td[9], tr[9], c1[3], c2[3];
-        or_coordinates(mu, tm);
-        float d[3] = {mu[0], mu[1], mu[2]};
-        float e1[3] = {tm[0], tm[1], tm[2]}, e2[3] = {tm[3], tm[4], tm[5]};
-        const float a0 = sh[k][0], a1 = sh[k][1];
-        const float len2 = a0 * a0 + a1 * a1;
-        if (len2 > 0.0f) {
-            /* the geodesic from mu along u = shift / |shift|; mu's axes parallel-transported along it */
-            const float len = sqrtf(len2);
-            const float sn = (float)sin((double)len), cs = (float)cos((double)len);
-            const float u0 = a0 / len, u1 = a1 / len;
-            float u[3];
-            for (int i = 0; i < 3; ++i) u[i] = u0 * tm[i] + u1 * tm[3 + i];
-            for (int i = 0; i < 3; ++i) d[i] = cs * mu[i] + sn * u[i];
-            for (int i = 0; i < 3; ++i) {
-                const float g = (cs - 1.0f) * u[i] - sn * mu[i];
-                e1[i] = tm[i] + u0 * g;
-                e2[i] = tm[3 + i] + u1 * g;
-            }
-        }
-        const float rn = 1.0f / sqrtf(li_dot3(d, d));
-        for (int i = 0; i < 3; ++i) d[i] = d[i] * rn;
-        or_coordinates(d, td);
-        li_l4_cong(li_dot3(td, e1), li_dot3(td, e2), li_dot3(td + 3, e1), li_dot3(td + 3, e2), sc[k][0], sc[k][1],
-                   sc[k][2], c1);
-        const float m[3] = {cr * d[0] - sr * d[1], sr * d[0] + cr * d[1], d[2]};
-        or_coordinates(m, tr);
-        const float r1[3] = {cr * td[0] - sr * td[1], sr * td[0] + cr * td[1], td[2]};
-        const float r2[3] = {cr * td[3] - sr * td[4], sr * td[3] + cr * td[4], td[5]};
-        li_l4_cong(li_dot3(tr, r1), li_dot3(tr, r2), li_dot3(tr + 3, r1), li_dot3(tr + 3, r2), c1[0], c1[1], c1[2],
-                   c2);
         w[j] = pw[k] / sum;
-        mean[3 * j] = m[0]; mean[3 * j + 1] = m[1]; mean[3 * j + 2] = m[2];
-        cov[4 * j] = c2[0]; cov[4 * j + 1] = c2[1]; cov[4 * j + 2] = c2[1]; cov[4 * j + 3] = c2[2];
+        li_l4_lobe(rec + LI_L4_REC * k + 3, sh[k][0], sh[k][1], sc[k], cr, sr, mean + 3 * j, cov + 4 * j);
     }
     return n;
 }
@@ -392,6 +419,142 @@ int or_learned4_conditional(const float* rec, int M, float alpha, const float wl
     FTZ_SCOPE;
     if (!(wl[2] > 0.0f)) return 0;
     return li_learned_conditional(rec, M, fl_acos(fminf(1.0f, wl[2])), alpha, wl, keep, w, mean, cov);
+}
+
+/* A learned BSDF over a condition of dimension C (2: an SDMM4, 3: the SDMM5 of
+ * bsdf.h:316-324, Phong's on (theta_i, specWeight, log exponent), phong.cpp:
+ * 75-90), conditioned on x[C] at local wi.  One record: the weight, the C
+ * condition means, the unit direction, the (C+2)x(C+2) covariance row-major
+ * over (c_0 .. c_{C-1}, t1, t2).  The reading of the absent sdmm-lib calls, as
+ * above, with
+ *   S_cc = L L^T by a lower Cholesky that reads the upper triangle; a pivot
+ *   not > 0: pi' = 0; pi' = pi N(x; mu_c, S_cc) with the normaliser
+ *   (2 pi)^(C/2) prod l_ii; z = L^-1 (x - mu_c), y = L^-T z; shift = S_dc y;
+ *   G = L^-1 S_cd, S'_dd = S_dd - G^T G (not PD: pi' = 0);
+ *   keep 1..8: create_conditional_pruned -- the `keep` largest pi' (ties: the
+ *   lower index); force >= 0 (the five-argument call's diffuse_component): that
+ *   component, if valid (force < M, pi' > 0) and not chosen before the last
+ *   place, takes the last place; keep 0: create_conditional, every pi' > 0 in
+ *   model order; renormalised.  Lobes as li_l4_lobe.  Returns the lobes
+ *   written, 0: no valid conditional. */
+#define LI_ND_MAXC 3
+#define LI_ND_REC(C) (1 + ((C) + 3) + ((C) + 2) * ((C) + 2))
+#define LI_ND_STRIDE (2 + LI_L4_MAX * LI_ND_REC(LI_ND_MAXC))   /* per BSDF: [C, M, records] */
+#define LI_PHONG_FORCE 1                                        /* phong.cpp:76 */
+static int li_learned_nd_conditional(const float* rec, int C, int M, const float* x, const float wl[3], int keep,
+                                     int force, float* w, float* mean, float* cov) {
+    if (C < 2 || C > LI_ND_MAXC) return 0;
+    const int D = C + 2, R = LI_ND_REC(C);
+    const float norm = (float)pow(2.0 * OR_PI, 0.5 * (double)C);
+    float pw[LI_L4_MAX], sh[LI_L4_MAX][2], sc[LI_L4_MAX][3];
+    if (M > LI_L4_MAX) M = LI_L4_MAX;
+    if (keep > LI_L4_MAX) keep = LI_L4_MAX;
+    for (int k = 0; k < M; ++k) {
+        const float* p = rec + R * k;
+        const float* S = p + 1 + C + 3;
+        float L[LI_ND_MAXC][LI_ND_MAXC], z[LI_ND_MAXC], y[LI_ND_MAXC], G[LI_ND_MAXC][2];
+        pw[k] = 0.0f;
+        sh[k][0] = sh[k][1] = 0.0f;
+        sc[k][0] = sc[k][1] = sc[k][2] = 0.0f;
+        /* row i of L from the rows above it */
+        float ldet = 1.0f;
+        int ok = 1;
+        for (int i = 0; i < C && ok; ++i) {
+            for (int j = 0; j < i; ++j) {
+                float a = S[D * j + i];
+                for (int l = 0; l < j; ++l) a = a - L[i][l] * L[j][l];
+                L[i][j] = a / L[j][j];
+            }
+            float piv = S[D * i + i];
+            for (int l = 0; l < i; ++l) piv = piv - L[i][l] * L[i][l];
+            if (!(piv > 0.0f)) { ok = 0; break; }
+            L[i][i] = sqrtf(piv);
+            ldet = ldet * L[i][i];
+        }
+        if (!ok) continue;
+        float maha = 0.0f;
+        for (int i = 0; i < C; ++i) {
+            float a = x[i] - p[1 + i];
+            for (int l = 0; l < i; ++l) a = a - L[i][l] * z[l];
+            z[i] = a / L[i][i];
+            maha = maha + z[i] * z[i];
+        }
+        const float dens = (float)exp((double)(-0.5f * maha)) / (norm * ldet);
+        for (int i = C - 1; i >= 0; --i) {
+            float a = z[i];
+            for (int l = i + 1; l < C; ++l) a = a - L[l][i] * y[l];
+            y[i] = a / L[i][i];
+        }
+        for (int t = 0; t < 2; ++t) {
+            const float* row = S + D * (C + t);   /* S_dc, tangent row t */
+            float a = row[0] * y[0];
+            for (int l = 1; l < C; ++l) a = a + row[l] * y[l];
+            sh[k][t] = a;
+            for (int i = 0; i < C; ++i) {         /* column t of G = L^-1 S_cd */
+                float b = S[D * i + C + t];
+                for (int l = 0; l < i; ++l) b = b - L[i][l] * G[l][t];
+                G[i][t] = b / L[i][i];
+            }
+        }
+        float g00 = G[0][0] * G[0][0], g01 = G[0][0] * G[0][1], g11 = G[0][1] * G[0][1];
+        for (int l = 1; l < C; ++l) {
+            g00 = g00 + G[l][0] * G[l][0];
+            g01 = g01 + G[l][0] * G[l][1];
+            g11 = g11 + G[l][1] * G[l][1];
+        }
+        const float s00 = S[D * C + C] - g00, s01 = S[D * C + C + 1] - g01, s11 = S[D * (C + 1) + C + 1] - g11;
+        if (!(s00 > 0.0f) || !(s00 * s11 - s01 * s01 > 0.0f)) continue;
+        sc[k][0] = s00;
+        sc[k][1] = s01;
+        sc[k][2] = s11;
+        pw[k] = p[0] * dens;
+    }
+    int sel[LI_L4_MAX], n = 0;
+    float sum = 0.0f;
+    if (keep == 0) {
+        for (int k = 0; k < M; ++k)
+            if (pw[k] > 0.0f) { sel[n++] = k; sum += pw[k]; }
+    } else {
+        int pending = force >= 0 && force < M && pw[force] > 0.0f;   /* the forced component still to be placed */
+        for (int slot = 0; slot < keep; ++slot) {
+            int best = -1;
+            if (pending && slot == keep - 1) {
+                best = force;
+            } else {
+                for (int k = 0; k < M; ++k) {
+                    int taken = 0;
+                    for (int t = 0; t < n; ++t) taken = taken || sel[t] == k;
+                    if (taken || !(pw[k] > 0.0f)) continue;
+                    if (best < 0 || pw[k] > pw[best]) best = k;
+                }
+            }
+            if (best < 0) break;
+            if (best == force) pending = 0;
+            sel[n++] = best;
+            sum += pw[best];
+        }
+    }
+    if (n == 0 || !(sum > 0.0f) || !(sum < INFINITY)) return 0;
+    float cr, sr;
+    li_l4_azimuth(wl, &cr, &sr);
+    for (int j = 0; j < n; ++j) {
+        const int k = sel[j];
+        w[j] = pw[k] / sum;
+        li_l4_lobe(rec + R * k + 1 + C, sh[k][0], sh[k][1], sc[k], cr, sr, mean + 3 * j, cov + 4 * j);
+    }
+    return n;
+}
+
+/* ctypes entry for the tests: the lobes of one model (M records of LI_ND_REC(C)
+ * floats) at local wi and the condition (theta_i, x_rest[0 .. C-2]) */
+int or_learned_nd_conditional(const float* rec, int C, int M, const float* x_rest, const float wl[3], int keep,
+                              int force, float* w, float* mean, float* cov) {
+    FTZ_SCOPE;
+    if (C < 2 || C > LI_ND_MAXC || M <= 0 || !(wl[2] > 0.0f)) return 0;
+    float x[LI_ND_MAXC];
+    x[0] = fl_acos(fminf(1.0f, wl[2]));
+    for (int i = 1; i < C; ++i) x[i] = x_rest[i - 1];
+    return li_learned_nd_conditional(rec, C, M, x, wl, keep, force, w, mean, cov);
 }
 
 /* Mitsuba coordinateSystem (s, t) of n */
@@ -427,6 +590,71 @@ static void li_cosine_hemisphere(float u0, float u1, float w[3]) {
     w[2] = z;
 }
 
+/* ---- modified Phong (bsdfs/phong.cpp), local frame, both components ----
+ * bp: [1..3] specularReflectance, [4] exponent, [5] m_specularSamplingWeight;
+ * rho: diffuseReflectance.  pow as (float)pow((double)x, (double)y). */
+static float fl_pow(float x, float y) { return (float)pow((double)x, (double)y); }
+/* Phong::eval (ESolidAngle, :171-196) into f; returns Phong::pdf (:198-230) */
+static float li_phong_eval_pdf(const float wi[3], const float wo[3], const float* bp, const float rho[3], float f[3]) {
+    const float inv_pi = 0.31830988618379067154f, inv_two_pi = 0.15915494309189533577f;
+    f[0] = f[1] = f[2] = 0.0f;
+    if (wi[2] <= 0.0f || wo[2] <= 0.0f) return 0.0f;
+    const float n = bp[4];
+    const float refl[3] = {-wi[0], -wi[1], wi[2]};   /* reflect(wi) (:167-169) */
+    const float ca = li_dot3(wo, refl);
+    float lobe = 0.0f, spec_prob = 0.0f;
+    if (ca > 0.0f) {
+        const float can = fl_pow(ca, n);
+        lobe = (n + 2.0f) * inv_two_pi * can;               /* :188 */
+        spec_prob = can * (n + 1.0f) / (2.0f * LI_PI_F);    /* :217-218 */
+    }
+    for (int ch = 0; ch < 3; ++ch) f[ch] = (bp[1 + ch] * lobe + rho[ch] * inv_pi) * wo[2];
+    return bp[5] * spec_prob + (1.0f - bp[5]) * (inv_pi * wo[2]);   /* :222-223 */
+}
+/* Phong::sample(bRec, pdf, sample) (:232-289), wi.z > 0: wo, eval / pdf into
+ * bw and the pdf; 0: void (weight 0, pdf 0; wo as far as it was formed).  The
+ * specular component is chosen with u0 <= weight && weight > 0 (the library's
+ * documented deviation: with weight 0 the reference divides 0 by 0 at u0 = 0). */
+static int li_phong_sample(const float wi[3], const float* bp, const float rho[3], float u0, float u1, float wo[3],
+                           float bw[3], float* pdf) {
+    const float n = bp[4], ssw = bp[5];
+    *pdf = 0.0f;
+    bw[0] = bw[1] = bw[2] = 0.0f;
+    if (ssw > 0.0f && u0 <= ssw) {
+        const float ux = u0 / ssw;                               /* :247 */
+        const float refl[3] = {-wi[0], -wi[1], wi[2]};
+        /* a lobe about (0, 0, 1) (:260-267), then Frame(R).toWorld (:270) */
+        const float cos_a = fl_pow(u1, 1.0f / (n + 1.0f));
+        const float sin_a = sqrtf(1.0f - fl_pow(u1, 2.0f / (n + 1.0f)));
+        const float phi = (2.0f * LI_PI_F) * ux;
+        const float lx = sin_a * fl_cos(phi), ly = sin_a * fl_sin(phi);
+        float s[3], t[3];
+        li_frame(refl, s, t);
+        for (int a = 0; a < 3; ++a) wo[a] = s[a] * lx + t[a] * ly + refl[a] * cos_a;
+        if (wo[2] <= 0.0f) return 0;                             /* :274-275 */
+    } else {
+        li_cosine_hemisphere((u0 - ssw) / (1.0f - ssw), u1, wo); /* :249-250, :277 */
+    }
+    float f[3];
+    const float p = li_phong_eval_pdf(wi, wo, bp, rho, f);
+    if (p == 0.0f) return 0;                                     /* :285-286 */
+    const float rp = 1.0f / p;   /* Spectrum / Float: times the reciprocal */
+    for (int ch = 0; ch < 3; ++ch) bw[ch] = f[ch] * rp;
+    *pdf = p;
+    return 1;
+}
+/* ctypes entry for the tests: u given -> the sample (s_wo, s_weight, s_pdf);
+ * wo_eval given -> eval and pdf there (e_f, e_pdf) */
+void or_bsdf_phong(const float* bp, const float rho[3], const float wi[3], const float* u, const float* wo_eval,
+                   float s_wo[3], float s_weight[3], float* s_pdf, float e_f[3], float* e_pdf) {
+    FTZ_SCOPE;
+    if (u) {
+        s_wo[0] = 0.0f; s_wo[1] = 0.0f; s_wo[2] = 1.0f;
+        li_phong_sample(wi, bp, rho, u[0], u[1], s_wo, s_weight, s_pdf);
+    }
+    if (wo_eval) *e_pdf = li_phong_eval_pdf(wi, wo_eval, bp, rho, e_f);
+}
+
 typedef struct {
     const li_scene* S;
     const float *mn, *mx;
@@ -440,11 +668,12 @@ typedef struct {
     const float *bw, *bmean, *bcov;
     const uint8_t* bdiff;
     int M, Kmax;
-    int lM;   /* the product's lobes per row: max(M, 2) with a conductor in the scene, else M */
+    int lM;   /* the product's lobes per row: max(M, 2) with a conductor or a Phong BSDF on some quad, else M */
     float* rec;
     int32_t* nv;
     float* L;        /* P x 3 radiance */
     int32_t* comps;  /* bounces x P */
+    int32_t* hit_bsdf;   /* bounces x P, optional: the BSDF a live bounce scattered at (-1: none) */
     int bounces;
 } li_job;
 
@@ -530,7 +759,7 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
     }
     int depth = q >= 0 ? 1 : -1;
     for (int b = 0; b < J->bounces; ++b) {
-        int32_t comp_out = -9;
+        int32_t comp_out = -9, bsdf_out = -1;
         if (depth >= 0) {
             /* loop head (:684-691), sampleSurface (:275-421) */
             int live = !(J->max_depth >= 0 && depth >= J->max_depth);
@@ -540,7 +769,9 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
             const float* bp = S->bpar ? S->bpar + 8 * QD->bsdf : NULL;
             const int plastic = bp && bp[0] == 1.0f;
             const int conductor = bp && bp[0] == 2.0f;
-            const int zero_spec = !(plastic || conductor) || (bp[1] == 0.0f && bp[2] == 0.0f && bp[3] == 0.0f);
+            const int phong = bp && bp[0] == 3.0f;
+            const int zero_spec =
+                !(plastic || conductor || phong) || (bp[1] == 0.0f && bp[2] == 0.0f && bp[3] == 0.0f);
             const int zero_diff = conductor || (rho[0] == 0.0f && rho[1] == 0.0f && rho[2] == 0.0f);
             const float wi[3] = {-d[0], -d[1], -d[2]};
             if (live && (!(li_dot3(wi, n) > 0.0f) || (zero_diff && zero_spec)))
@@ -549,6 +780,7 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                 depth = -1;
             } else {
                 const uint32_t stream = 1u + (uint32_t)b;
+                bsdf_out = QD->bsdf;
                 const float c[3] = {(p[0] - S->smin[0]) / S->snorm, (p[1] - S->smin[1]) / S->snorm,
                                     (p[2] - S->smin[2]) / S->snorm};
                 float s[3], tt[3], w[3];
@@ -579,6 +811,10 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                     const float wl[3] = {li_dot3(wi, s), li_dot3(wi, tt), li_dot3(wi, n)};
                     li_conductor_sample(wl, bp, or_rng_uniform(J->seed, gp, stream, 0),
                                         or_rng_uniform(J->seed, gp, stream, 1), w, bw, &bpdf);
+                } else if (phong) {
+                    const float wl[3] = {li_dot3(wi, s), li_dot3(wi, tt), li_dot3(wi, n)};
+                    li_phong_sample(wl, bp, rho, or_rng_uniform(J->seed, gp, stream, 0),
+                                    or_rng_uniform(J->seed, gp, stream, 1), w, bw, &bpdf);
                 } else {
                     li_cosine_hemisphere(or_rng_uniform(J->seed, gp, stream, 0),
                                          or_rng_uniform(J->seed, gp, stream, 1), w);
@@ -598,7 +834,8 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                     if (m) {
                         const float F[9] = {s[0], tt[0], n[0], s[1], tt[1], n[1], s[2], tt[2], n[2]};
                         float hq, gw[64], gm[64 * 3], gc[64 * 4];
-                        int glossy = 0;   /* 1: the conductor's lobes, -1: a conductor without a valid getDMM */
+                        /* 1: the conductor's / Phong's own lobes, -1: such a BSDF without a valid getDMM */
+                        int glossy = 0;
                         if (conductor && J->product) {
                             const float wl[3] = {li_dot3(wi, s), li_dot3(wi, tt), li_dot3(wi, n)};
                             const float* lm = J->S->lmodel ? J->S->lmodel + (size_t)LI_L4_STRIDE * QD->bsdf : NULL;
@@ -607,6 +844,23 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                             if (LM > 0)
                                 kept = li_learned_conditional(lm + 1, LM, fl_acos(fminf(1.0f, wl[2])), bp[6], wl,
                                                               LI_L4_KEEP, gw, gm, gc);
+                            for (int l = kept; l < J->lM; ++l) gw[l] = 0.0f;
+                            glossy = kept > 0 ? 1 : -1;
+                        } else if (phong && J->product) {
+                            /* Phong::getDMM (phong.cpp:75-90): the SDMM5 at (theta_i, the largest
+                             * specular channel, log max(1, exponent)), pruned to 2 with the diffuse
+                             * component kept */
+                            const float wl[3] = {li_dot3(wi, s), li_dot3(wi, tt), li_dot3(wi, n)};
+                            const float* lm =
+                                J->S->lmodel_nd ? J->S->lmodel_nd + (size_t)LI_ND_STRIDE * QD->bsdf : NULL;
+                            const int LM = lm ? (int)lm[1] : 0;
+                            int kept = 0;
+                            if (LM > 0) {
+                                const float x[3] = {fl_acos(fminf(1.0f, wl[2])), fmaxf(bp[1], fmaxf(bp[2], bp[3])),
+                                                    fl_log(fmaxf(1.0f, bp[4]))};
+                                kept = li_learned_nd_conditional(lm + 2, (int)lm[0], LM, x, wl, LI_L4_KEEP,
+                                                                 LI_PHONG_FORCE, gw, gm, gc);
+                            }
                             for (int l = kept; l < J->lM; ++l) gw[l] = 0.0f;
                             glossy = kept > 0 ? 1 : -1;
                         }
@@ -649,7 +903,7 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                         mis_pdf = bpdf > 0.0f ? h * bpdf + (1.0f - h) * gpdf : 0.0f;
                         for (int ch = 0; ch < 3; ++ch) weight[ch] = mis_pdf == 0.0f ? 0.0f : (bw[ch] * bpdf) * (1.0f / mis_pdf);
                     }
-                } else if (conductor) {
+                } else if (conductor || phong) {
                     if (comp == -1 || comp == -2) {
                         wo[0] = bdir[0]; wo[1] = bdir[1]; wo[2] = bdir[2];
                         if (comp == -1) {
@@ -666,7 +920,9 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                         const float wol[3] = {li_dot3(wo, s), li_dot3(wo, tt), li_dot3(wo, n)};
                         const int zero = (wo[0] == 0.0f && wo[1] == 0.0f && wo[2] == 0.0f) || !isfinite(wol[2]);
                         float f[3] = {0.0f, 0.0f, 0.0f};
-                        const float bsdf_pdf = zero ? 0.0f : li_conductor_eval_pdf(wil, wol, bp, f);
+                        const float bsdf_pdf = zero    ? 0.0f
+                                               : phong ? li_phong_eval_pdf(wil, wol, bp, rho, f)
+                                                       : li_conductor_eval_pdf(wil, wol, bp, f);
                         mis_pdf = bsdf_pdf > 0.0f ? h * bsdf_pdf + (1.0f - h) * gpdf : 0.0f;
                         for (int ch = 0; ch < 3; ++ch) weight[ch] = mis_pdf == 0.0f ? 0.0f : f[ch] * (1.0f / mis_pdf);
                     }
@@ -746,6 +1002,7 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
             }
         }
         if (J->comps) J->comps[(int64_t)b * J->P + i] = comp_out;
+        if (J->hit_bsdf) J->hit_bsdf[(int64_t)b * J->P + i] = bsdf_out;
     }
     J->nv[i] = nv;
     for (int ch = 0; ch < 3; ++ch) J->L[3 * i + ch] = Li[ch];
@@ -779,7 +1036,8 @@ int or_li_render(const float* quads, const int32_t* flip, const int32_t* bsdf, i
                  int guided, int spp, int max_depth, int rr_depth, float h, int V, uint64_t seed, int64_t pix_begin,
                  int64_t pix_end, int product, const float* bw, const float* bmean, const float* bcov,
                  const uint8_t* bdiff, int M, int Kmax, float* image, float* image_sqr, float* rec, int32_t* nv,
-                 int32_t* comps, int nthreads, const float* learned_models) {
+                 int32_t* comps, int nthreads, const float* learned_models, const float* learned_models_nd,
+                 int32_t* hit_bsdf) {
     FTZ_SCOPE;
     li_scene S;
     if (!li_scene_build(&S, quads, flip, bsdf, n_quads, refl, bsdf_params, emitter, rad, cam, fov, near_clip, width,
@@ -788,6 +1046,7 @@ int or_li_render(const float* quads, const int32_t* flip, const int32_t* bsdf, i
         return -1;
     }
     S.lmodel = learned_models;   /* LI_L4_STRIDE floats per BSDF, NULL: none */
+    S.lmodel_nd = learned_models_nd;   /* LI_ND_STRIDE floats per BSDF, NULL: none */
     const int64_t npix = pix_end - pix_begin, P = npix * spp;
     li_job J;
     memset(&J, 0, sizeof(J));
@@ -797,11 +1056,16 @@ int or_li_render(const float* quads, const int32_t* flip, const int32_t* bsdf, i
     J.V = V; J.product = product; J.h = h; J.seed = seed;
     J.path0 = pix_begin * spp; J.P = P;
     J.bw = bw; J.bmean = bmean; J.bcov = bcov; J.bdiff = bdiff; J.M = M; J.Kmax = Kmax;
+    /* the device's rule (sdmm_scene_create: a conductor or a Phong BSDF on some
+     * quad, with or without a learned model, gives every compact query its own
+     * row of max(M, 2) lobes; extend_learned, render_api.cpp) */
     J.lM = M;
     if (bsdf_params)
-        for (int q = 0; q < n_quads; ++q)
-            if (bsdf_params[8 * bsdf[q]] == 2.0f && J.lM < LI_L4_KEEP) J.lM = LI_L4_KEEP;
-    J.rec = rec; J.nv = nv; J.comps = comps;
+        for (int q = 0; q < n_quads; ++q) {
+            const float kind = bsdf_params[8 * bsdf[q]];
+            if ((kind == 2.0f || kind == 3.0f) && J.lM < LI_L4_KEEP) J.lM = LI_L4_KEEP;
+        }
+    J.rec = rec; J.nv = nv; J.comps = comps; J.hit_bsdf = hit_bsdf;
     J.L = (float*)malloc(sizeof(float) * 3 * (size_t)(P > 0 ? P : 1));
     J.bounces = max_depth > 0 ? max_depth - 1 : V;
     if (nthreads < 1) nthreads = 1;

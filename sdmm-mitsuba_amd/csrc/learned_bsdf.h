@@ -1,7 +1,7 @@
 // learned_bsdf.h -- a glossy material's learned BSDF conditioned per bounce
 // (host + device; render.hip's product bounces and the host ABI
 // sdmm_learned4_conditional / sdmm_learned_conditional share this code,
-// oracle/sdmm_oracle_li.inc restates the SDMM4 part in C).
+// oracle/sdmm_oracle_li.inc restates both conditionals in C).
 //
 // Reference: RoughConductor::getDMM (mitsuba/src/bsdfs/roughconductor.cpp:
 // 182-194) conditions the material's learned SDMM4 -- BSDF::SDMM4, a

@@ -3,7 +3,9 @@ its learned SDMM5 in the product bounce (Phong::getDMM, phong.cpp:75-90:
 conditioned per bounce on (theta_i, specWeight, log exponent), pruned to 2
 with the diffuse component forced, then rotate_to_wo as for the conductor).
 
-oracle/ has no Phong Li, so the render is pinned by unbiasedness: a Phong
+The path-by-path comparison with the CPU Li is tests/test_gpu_li_oracle_phong.py
+(unguided bit-exact, guided and product >= 99 % of the paths); here the render
+is pinned by unbiasedness: a Phong
 BSDF with no specular part is the diffuse BSDF, and the product render agrees
 with BSDF-only sampling of the same scene (4 sigma over the pixel means, the
 form of tests/test_gpu_li.py); the training records still equal the

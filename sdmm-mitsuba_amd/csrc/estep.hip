@@ -237,6 +237,19 @@ __device__ __forceinline__ SampleBlock load_block(const SamplesDev& s, int64_t b
     return b;
 }
 
+// A sample with a NaN or Inf coordinate (the reference checks only the weight,
+// stepwise_tangent.h:445-449): 1/S' is not finite, every posterior is zeroed
+// (mixture_model.h:182-191) and calculateStats skips the sample (:312) while
+// sumWeights still counts its weight.  The statistics kernels form v = 0 for
+// it, but v * (x - mu) or v * tangent would be 0 * NaN = NaN in every
+// accumulator of the lane, so they stage such a sample as the failed log map
+// d = 0 at the origin (all pdfs 0, finite tangents) with a NaN hpdf, which
+// keeps 1/S' non-finite for a diffuse one too: nothing passes, gamma_h = 0.
+__device__ __forceinline__ bool dead_sample(float x0, float x1, float x2, float x3, float x4, float x5) {
+    return !(__builtin_isfinite(x0) && __builtin_isfinite(x1) && __builtin_isfinite(x2) &&
+             __builtin_isfinite(x3) && __builtin_isfinite(x4) && __builtin_isfinite(x5));
+}
+
 template <int LPS>
 __device__ __forceinline__ float bcast(float v, int src) {
     if constexpr (LPS == 64)
@@ -275,7 +288,14 @@ __device__ __forceinline__ void run_block(SampleBlock b, int64_t blk, int64_t s1
     constexpr int SPW = 64 / LPS;
     const int cnt = (s1 - blk < 64) ? (int)(s1 - blk) : 64;
     const bool has_h = s.hpdf != nullptr, has_d = s.isDiffuse != nullptr;
-    if constexpr (WANT_CD) b.cd = half_defect(b.x3, b.x4, b.x5);   // once per sample (its own lane)
+    if constexpr (WANT_CD) {
+        // once per sample (its own lane)
+        if (dead_sample(b.x0, b.x1, b.x2, b.x3, b.x4, b.x5)) {
+            b.x0 = b.x1 = b.x2 = b.x3 = b.x4 = b.x5 = 0.0f;
+            b.h = __builtin_nanf("");
+        }
+        b.cd = half_defect(b.x3, b.x4, b.x5);
+    }
     for (int t = 0; t < cnt; t += SPW) {
         // block lane t+g held sample blk+t+g (clamped to s1-1 past the end)
         int64_t si = blk + t + g;
@@ -999,9 +1019,12 @@ estep_stats_tile_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
                 const int64_t si = (blk + lane < s1) ? blk + lane : s1 - 1;
                 const int sh = 8 * (int)((uintptr_t)(s.isDiffuse + si) & 3);
                 const bool dif = has_d && ((A.diff >> sh) & 0xff) != 0;
-                blk_lds[lane][0] = float4{A.x0, A.x1, A.x2, A.x3};
-                blk_lds[lane][1] = float4{A.x4, A.x5, has_h ? A.h : 0.0f, dif ? 1.0f : 0.0f};
-                w_lds[lane] = float2{A.w, half_defect(A.x3, A.x4, A.x5)};
+                const bool dead = dead_sample(A.x0, A.x1, A.x2, A.x3, A.x4, A.x5);
+                const float d0 = dead ? 0.0f : A.x3, d1 = dead ? 0.0f : A.x4, d2 = dead ? 0.0f : A.x5;
+                const float hp = dead ? __builtin_nanf("") : (has_h ? A.h : 0.0f);
+                blk_lds[lane][0] = float4{dead ? 0.0f : A.x0, dead ? 0.0f : A.x1, dead ? 0.0f : A.x2, d0};
+                blk_lds[lane][1] = float4{d1, d2, hp, dif ? 1.0f : 0.0f};
+                w_lds[lane] = float2{A.w, half_defect(d0, d1, d2)};
             }
             A = load_block(s, blk + 64, s1, lane);
             const int cnt = (s1 - blk < 64) ? (int)(s1 - blk) : 64;

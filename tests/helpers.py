@@ -70,10 +70,23 @@ def explained_rows(post, q, c, qmax=100.0, cmin=1e-2, pmin=1e-7):
     return (qm < qmax) & (post.sum(1) > 0) & cond
 
 
-def estep_f64(mix_params: dict, x, w, hpdf=None, is_diffuse=None, h=0.5, chunk=2048):
+def angle_over_sin(cc, quirk=True):
+    """theta / sin(theta) for cos(theta) = cc <= 1 (mvtn.h:157-164).  quirk:
+    the reference's `sin < 1e-3 -> 1`; without it the plain ratio (1 only at
+    sin == 0), which is what a path that misses the quirk evaluates."""
+    th = np.arccos(np.clip(cc, -1, 1))
+    s = np.sqrt(np.maximum(1 - cc * cc, 0))
+    return np.where((s < 1e-3) if quirk else (s <= 0), 1.0, th / np.where(s > 0, s, 1))
+
+
+def estep_f64(mix_params: dict, x, w, hpdf=None, is_diffuse=None, h=0.5, chunk=2048, quirk=True):
     """calculateStats + sumWeights (stepwise_tangent.h:270-353, :462-475) in
     float64 from the float mixture parameters.  Returns the oracle stats
-    layout [H, weightSum, W(K), M(5K), C(25K)]."""
+    layout [H, weightSum, W(K), M(5K), C(25K)].  A sample whose posterior is
+    zeroed (1/S' not finite: a NaN or Inf coordinate, mixture_model.h:182-191)
+    is skipped by `posterior < 1e-10 -> continue` (:312) whatever its tangent
+    holds; its finite weight still counts in weightSum.  quirk=False: the
+    angle function without the sin < 1e-3 quirk (angle_over_sin)."""
     wt = np.asarray(mix_params["weights"], np.float64)
     mean = np.asarray(mix_params["mean"], np.float64).reshape(-1, 6)
     to = np.asarray(mix_params["to"], np.float64).reshape(-1, 3, 3)
@@ -99,10 +112,8 @@ def estep_f64(mix_params: dict, x, w, hpdf=None, is_diffuse=None, h=0.5, chunk=2
         r = np.einsum("kij,nj->nki", to, d)
         c = r[..., 2]
         bad = (c <= -1) | (np.abs(d).sum(1) == 0)[:, None]
-        cc = np.minimum(c, 1.0)
-        th = np.arccos(np.clip(cc, -1, 1))
-        s = np.sqrt(np.maximum(1 - cc * cc, 0))
-        aa = np.where(s < 1e-3, 1.0, th / np.where(s > 0, s, 1))
+        with np.errstate(invalid="ignore"):
+            aa = angle_over_sin(np.minimum(c, 1.0), quirk)
         tdir = r[..., :2] * aa[..., None]
         tau_rel = np.concatenate([p[:, None, :] - mean[None, :, :3], tdir], -1)
         u = np.einsum("kij,nkj->nki", Li, tau_rel)
@@ -123,7 +134,8 @@ def estep_f64(mix_params: dict, x, w, hpdf=None, is_diffuse=None, h=0.5, chunk=2
         with np.errstate(invalid="ignore"):
             v = np.where((gam >= 1e-10) & use[:, None], ww[:, None] * gam, 0.0)
         tau = np.concatenate([np.broadcast_to(p[:, None, :], tdir.shape[:2] + (3,)), tdir], -1)
-        tau = np.where(bad[..., None], 0.0, tau)
+        # a skipped pair (v == 0) adds nothing: 0 * NaN must not reach the sums
+        tau = np.where(bad[..., None] | (v == 0)[..., None], 0.0, tau)
         W += v.sum(0)
         M += np.einsum("nk,nki->ki", v, tau)
         C += np.einsum("nk,nki,nkj->kij", v, tau, tau)

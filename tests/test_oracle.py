@@ -287,3 +287,39 @@ def test_float_division_by_double_reciprocal_is_exact():
         got = (x.astype(np.float64) * (1.0 / d.astype(np.float64))).astype(np.float32)
     ok = np.isfinite(ref) & (np.abs(ref) >= np.finfo(np.float32).tiny)
     np.testing.assert_array_equal(got[ok], ref[ok])
+
+
+def test_estep_f64_skips_nonfinite_rows_like_the_oracle(oracle, synth):
+    """A sample with a NaN / Inf coordinate and a finite weight has its
+    posterior zeroed and is skipped by calculateStats (sdmm_oracle_em.inc:
+    posterior < 1e-10 -> continue) while sumWeights counts it.  helpers.estep_f64
+    -- the fp64 reference of the GPU statistics tests -- does the same: no
+    0 * NaN reaches its sums, it agrees with the oracle on such a batch, equals
+    the batch with those rows' weights zeroed (but for weightSum)."""
+    from helpers import estep_f64
+    K, N = 16, 1001
+    b = synth.em_batch(N, 128)
+    pos, nrm = synth.model_seed_points(b, K)
+    om, _ = oracle.hemisphere_init(K // 8, pos, nrm, synth.DEPTH_PRIOR, synth.SPATIAL_DISTANCE,
+                                   synth.SEED_MODEL, mode=1)
+    p = {k: getattr(om, k) for k in ("weights", "mean", "to", "cholLInv", "detInv")}
+    x, w = b["x"].copy(), b["w"].copy()
+    rows = np.zeros(N, bool)
+    x[0:3, 1::97] = np.nan
+    x[3:6, 2::97] = np.nan
+    x[0, 3::97] = np.inf
+    for a in (1, 2, 3):
+        rows[a::97] = True
+    w[rows & ~(np.isfinite(w) & (w != 0))] = 1.5
+    with np.errstate(invalid="ignore"):
+        got = estep_f64(p, x, w)
+    ref = oracle.calculate_stats(om, oracle.Samples(x, w), accurate=True)
+    assert np.isfinite(got).all() and np.isfinite(ref).all()
+    fin = np.isfinite(w)
+    np.testing.assert_allclose(got[1], w[fin].astype(np.float64).sum(), rtol=1e-12)
+    # the fp32 oracle's own distance from fp64 on finite input is ~1e-7 of the total weight
+    assert np.abs(got - ref).max() <= 1e-6 * got[1]
+    x0 = np.where(rows[None, :], 0.5, x).astype(np.float32)       # finite stand-ins, weight 0
+    zeroed = estep_f64(p, x0, np.where(rows, np.float32(0), w))
+    np.testing.assert_array_equal(got[2:], zeroed[2:])
+    np.testing.assert_array_equal(got[0], zeroed[0])

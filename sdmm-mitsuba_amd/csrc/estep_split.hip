@@ -38,8 +38,10 @@
 // E-step record and read as one ds_read_b128 per fragment, conflict-free.  The
 // D layout gives each lane one component (col = lane & 15) of four samples
 // (rows 4 (lane >> 4) + j); the nonlinear rest of the pair math (angle, exp,
-// pdf) runs packed over sample pairs (j, j+1), the posterior normaliser is a
-// DPP row sum, and a store writes four 64-byte row segments.
+// pdf) runs packed over sample pairs (j, j+1), the posterior normaliser sums
+// the lane's own 4 R components and then the sample's four lane groups by two
+// row swaps (v_permlane16_swap, v_permlane32_swap), and the rows go out as
+// 16-B stores (K = 128: staged through LDS into 256-B half rows).
 #include "sdmm_device.h"
 
 namespace sdmm {
@@ -152,17 +154,19 @@ __device__ __forceinline__ u4 coef_frag(const float* __restrict__ ep, int Kp, in
     return u4{0u, 0u, h0 | (h1 << 16), h2 | (nh << 16)};
 }
 
-// sum over the 16 lanes of a DPP row; every lane of the row gets the sum
-template <int CTRL>
-__device__ __forceinline__ float dppf(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float row_sum16(float x) {
-    x += dppf<0xB1>(x);    // quad_perm [1,0,3,2]
-    x += dppf<0x4E>(x);    // quad_perm [2,3,0,1]
-    x += dppf<0x141>(x);   // row_half_mirror
-    x += dppf<0x140>(x);   // row_mirror
-    return x;
+// x + (x of lane ^ 16), then + (that of lane ^ 32): the sum over the four
+// 16-lane rows, in every lane.  The swaps exchange the odd rows (the upper
+// half) of one copy with the even rows (the lower half) of the other, so the
+// two results are the lane's own value and its partner's in one VALU each (no
+// LDS crossbar, no lane-index arithmetic, no lgkmcnt wait); builtins, so the
+// compiler places the VALU-write hazard waits.
+__device__ __forceinline__ float rows_sum4(float x) {
+    const unsigned b = __builtin_bit_cast(unsigned, x);
+    const auto p = __builtin_amdgcn_permlane16_swap(b, b, false, false);
+    const float y = __builtin_bit_cast(float, (unsigned)p[0]) + __builtin_bit_cast(float, (unsigned)p[1]);
+    const unsigned c = __builtin_bit_cast(unsigned, y);
+    const auto q = __builtin_amdgcn_permlane32_swap(c, c, false, false);
+    return __builtin_bit_cast(float, (unsigned)q[0]) + __builtin_bit_cast(float, (unsigned)q[1]);
 }
 
 // pi_k pdf_k of the four (sample, component) pairs of one D fragment, as two
@@ -384,7 +388,6 @@ estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * WPB + wid;
     // the launch's 16-sample tiles dealt round robin over its waves (one round
     // of resident waves: each workgroup builds the coefficient image once):
     // wave w serves tiles w, w + nwaves, ..., so the waves running at one time
@@ -392,8 +395,32 @@ estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
     // 2048 waves' concurrent rows 256 KB apart -- the same HBM channel bits --
     // and one configuration ran 170-190 or 340-370 us per launch depending on
     // where the output buffer landed.)
+    // Waves are numbered in quads across the workgroups (nwaves = WPB gridDim):
+    // waves 4 q .. 4 q + 3 of a workgroup, one per SIMD, take four neighbouring
+    // tiles, and quad q of workgroup b comes before quad q + 1 of any.  The
+    // T mod nwaves waves that serve one tile more are then the first quads of
+    // EVERY workgroup, evenly over the SIMDs, and not all WPB waves of the
+    // first workgroups (block WPB + wid gave 85 CUs 66 tiles per SIMD and the
+    // rest 63 at N = 2^20; now 64 everywhere).  A quad and not single waves
+    // (wid gridDim + block): a tile reads 64 B of each fp32 plane and 16 B of
+    // the flag bytes, and with neighbouring tiles on different workgroups
+    // (other XCDs' L2s) every 128-B line was fetched twice, the flags' eight
+    // times: 67.6 against 31.2 MB read per launch at N = 2^20 (FETCH_SIZE).
+    static_assert(WPB % 4 == 0, "the deal numbers a workgroup's waves in quads");
+    const int64_t wave = 4 * ((int64_t)(wid >> 2) * gridDim.x + blockIdx.x) + (wid & 3);
     const int64_t s0 = 16 * wave, step = 16 * nwaves, s1 = n;
     if (wave >= nwaves || s0 >= n) return;
+    // The wave's run in 32-bit counts (SALU compares; there is no 64-bit
+    // scalar order compare): jfull tiles of 16 rows, then at most one that
+    // crosses s1 with rows_last rows (the next one lies wholly past the end:
+    // step >= 16), nit tiles in all.
+    const uint64_t span = (uint64_t)(s1 - s0), whole = span - 16;
+    const int jfull = span < 16          ? 0
+                      : (whole >> 32) == 0 ? (int)((uint32_t)whole / (uint32_t)step) + 1
+                                           : (int)(whole / (uint64_t)step) + 1;
+    const int64_t tl = s0 + jfull * step;   // the first tile that is not whole
+    const int rows_last = tl < s1 ? (int)(s1 - tl) : 0;
+    const int nit = jfull + (rows_last > 0 ? 1 : 0);
 
     // MFMA D[component][sample] = A[component][k] . B[k][sample]: A = the
     // coefficient fragment (lane: component 16 r + (lane & 15), k group
@@ -416,12 +443,27 @@ estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
                                                  : (has_d ? (const float*)s.isDiffuse : s.x[0]));
     const int sh1 = byteplane ? 0 : 2;
     const unsigned ring_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) u4*)ring;
-    auto dma = [&](int64_t t, int slot) __attribute__((always_inline)) {
-        int64_t i = t + sl;
-        i = (i < s1) ? i : s1 - 1;   // past the end: a valid sample, never stored
-        const uintptr_t a0 = src0 + ((uintptr_t)i << 2);
-        const uintptr_t a1 = (src1 + ((uintptr_t)i << sh1)) & ~(uintptr_t)3;
-        dma_pair(a0, a1, ring_lds + (unsigned)slot * (kFeatSlotU4 * 16u));
+    // The lane's two source addresses run with the tiles: dma() is called for
+    // the wave's tiles 0, 1, ... in order and advances them by the step (32
+    // bits: the launcher bounds nwaves), the byte plane's in bytes.  A tile
+    // that is not whole (wave-uniform: the end of the wave's run) reads the
+    // clamped samples of tile jfull instead -- past the end any valid sample
+    // does, those records are never used -- and the branch is kept a branch
+    // (the empty asm: not four selects on every tile).
+    uintptr_t dp0 = src0 + ((uintptr_t)(s0 + sl) << 2);
+    uintptr_t dp1 = src1 + ((uintptr_t)(s0 + sl) << sh1);
+    const unsigned dstep0 = (unsigned)step << 2, dstep1 = (unsigned)step << sh1;
+    const int64_t il = tl + sl < s1 ? tl + sl : s1 - 1;
+    const uintptr_t last0 = src0 + ((uintptr_t)il << 2), last1 = src1 + ((uintptr_t)il << sh1);
+    auto dma = [&](int j, int slot) __attribute__((always_inline)) {
+        if (j >= jfull) {
+            asm volatile("");
+            dp0 = last0;
+            dp1 = last1;
+        }
+        dma_pair(dp0, dp1 & ~(uintptr_t)3, ring_lds + (unsigned)slot * (kFeatSlotU4 * 16u));
+        dp0 += dstep0;
+        dp1 += dstep1;
     };
 
     auto pfrag = [&](const float (&p3)[3]) __attribute__((always_inline)) {
@@ -443,21 +485,30 @@ estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
     // The rows of tile t are stored at the top of the next tile (flush), after
     // the DMA of the features kFeatAhead tiles ahead; a full flush is exactly
     // R store instructions (the count read_feat_counted relies on).
+    // Row addresses: the tile's first row is a wave-uniform 64-bit base (SGPRs,
+    // advanced by the step's rows each tile) and the lane adds a 32-bit byte
+    // offset inside the tile, fixed before the loop (at most 16 rows of K
+    // floats: small for any n, nothing here is a product with a row index).
+    // A full tile has K = 16 R, so its offsets are constants of the lane.
     float pdf[R][4];
     float gsc_p = 0.0f;
     bool full_p = false;
-    int64_t tp = -1;
+    char* rowp = nullptr;   // the pending tile's first row (none yet)
+    int rows_p = 0;         // ... and its rows below s1 (16 unless it crosses s1)
+    char* rowt = (char*)(resp + s0 * (int64_t)K);
+    const int64_t rowstep = step * (int64_t)K * 4;
+    const unsigned voff = (unsigned)(col * K + 4 * g) * 4u;                     // row col, block 0's 16 B
+    const unsigned voff8 = (unsigned)(g * (16 * R) + 4 * col) * 4u;             // R = 8: row g, 16-B chunk col
     auto flush = [&]() __attribute__((always_inline)) {
-        if (tp < 0) return;
+        if (rowp == nullptr) return;
         if (kDiagNoStore && gsc_p != -1.0f) return;   // (never -1: the rows stay live)
-        float* row = resp + (tp + col) * (int64_t)K + 4 * g;
         if (full_p && R != 8) {
             // one 16-B store per block: a sample's 64-B row segment per 4 lanes
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const f2 lo = f2{pdf[r][0], pdf[r][1]} * spl(gsc_p);
                 const f2 hi = f2{pdf[r][2], pdf[r][3]} * spl(gsc_p);
-                __builtin_nontemporal_store(f4{lo.x, lo.y, hi.x, hi.y}, (f4*)(row + 16 * r));
+                __builtin_nontemporal_store(f4{lo.x, lo.y, hi.x, hi.y}, (f4*)(rowp + 64 * r + voff));
             }
         } else if (full_p) {
             // R = 8: rows through LDS, half a row (blocks 4h .. 4h+3, 256 B) at a
@@ -466,6 +517,17 @@ estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
             // whole lines); staged, every store writes four contiguous 256-B
             // half rows.  16-B chunk c of row i sits at chunk c ^ i (conflict-
             // free writes and reads).
+            // (the empty asm statements: the offset's zero extension stays in
+            // this block, where instruction selection can fold it into the
+            // store's SGPR-base form -- hoisted out of the loop it costs a
+            // 64-bit add per tile -- and rows 8 .. 15 get a scalar base of
+            // their own, since the eight constants, rows 4 i and half h, do
+            // not all fit the store's 13-bit offset)
+            unsigned vo = voff8;
+            asm volatile("" : "+v"(vo));
+            unsigned up = 8 * (16 * R) * 4;
+            asm volatile("" : "+s"(up));
+            char* const upper = rowp + up;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -480,30 +542,30 @@ estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
                 for (int i = 0; i < 4; ++i) {
                     const int rw = g + 4 * i, ch = col;
                     const f4 v = st[rw * 16 + (ch ^ rw)];
-                    __builtin_nontemporal_store(v, (f4*)(resp + (tp + rw) * (int64_t)K + 64 * h + 4 * ch));
+                    __builtin_nontemporal_store(v, (f4*)((i < 2 ? rowp : upper) + vo + (4 * (i & 1) * (16 * R) + 64 * h) * 4));
                 }
                 __builtin_amdgcn_wave_barrier();
             }
-        } else if (tp + col < s1) {
+        } else if (col < rows_p) {
 #pragma unroll
             for (int r = 0; r < R; ++r)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float o = gsc_p != 0.0f ? pdf[r][j] * gsc_p : 0.0f;
-                    if (16 * r + 4 * g + j < K) __builtin_nontemporal_store(o, row + 16 * r + j);
+                    if (16 * r + 4 * g + j < K) __builtin_nontemporal_store(o, (float*)(rowp + (16 * r + j) * 4 + voff));
                 }
         }
     };
 
     // prologue: the first kFeatAhead tiles' features in flight
 #pragma unroll
-    for (int a = 0; a < kFeatAhead; ++a) dma(s0 + a * step, a);
+    for (int a = 0; a < kFeatAhead; ++a) dma(a, a);
     unsigned hist = 0;   // bit j: the flush j iterations back was full
-    int it = 0;
-    for (int64_t t = s0; t < s1; t += step, ++it) {
+    unsigned tlow = (unsigned)s0;   // the tile's first sample, low bits
+    for (int it = 0; it < nit; ++it, tlow += (unsigned)step) {
         const int slot = it % kFeatSlots;
-        dma(t + kFeatAhead * step, (it + kFeatAhead) % kFeatSlots);   // clamped past the end
-        if (tp >= 0) hist = (hist << 1) | (full_p ? 1u : 0u);
+        dma(it + kFeatAhead, (it + kFeatAhead) % kFeatSlots);   // clamped past the end
+        if (rowp != nullptr) hist = (hist << 1) | (full_p ? 1u : 0u);
         flush();                                                       // tile t - step's rows
         const int k = it < kFeatAhead + 1 ? it : kFeatAhead + 1;
         const unsigned need = (1u << k) - 1u;
@@ -514,8 +576,13 @@ estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
         const float D3[3] = {fa.w, fb.x, fb.y};
         // d == 0 fails every log map (mvtn.h:152-154)
         const bool dzero = D3[0] == 0.0f && D3[1] == 0.0f && D3[2] == 0.0f;
-        const int64_t ic = (t + col < s1) ? t + col : s1 - 1;
-        const bool dif = has_d && ((fbits(fb.w) >> (8 * (int)((uintptr_t)(s.isDiffuse + ic) & 3))) & 0xffu) != 0u;
+        // the tile's rows below s1 (wave-uniform) and the sample this lane's
+        // record holds (the DMA's clamp); its flag byte's place in the dword
+        // needs the low address bits only
+        const int rows = it < jfull ? 16 : rows_last;
+        const unsigned cc = (unsigned)(col < rows ? col : rows - 1);
+        const unsigned fsh = (((unsigned)(uintptr_t)s.isDiffuse + tlow + cc) & 3u) << 3;
+        const bool dif = has_d && ((fbits(fb.w) >> fsh) & 0xffu) != 0u;
         const float hp = has_h ? fb.z : 0.0f;
         const bf8 Bd = a_frag(D3, g, false);
         const bf8 Bs = pfrag(P3);
@@ -589,16 +656,17 @@ estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
         // posterior normalisation of sample col (mixture_model.h:170-191): the
         // lane's 4 R components, then the four lane groups of the sample
         float S = (acc.x + acc.y) + (acc2.x + acc2.y);
-        S += __shfl_xor(S, 16);
-        S += __shfl_xor(S, 32);
+        S = rows_sum4(S);
         const float S2 = dif ? fmaf(1.0f - kHeuristicWeight, S, kHeuristicWeight * hp) : S;
         const float inv = __builtin_amdgcn_rcpf(S2);
         const bool fin = __builtin_isfinite(inv) && !dzero;
         gsc_p = fin ? (dif ? inv * (1.0f - kHeuristicWeight) : inv) : 0.0f;
         // a non-finite sum means a non-finite pdf (NaN/inf input): zero rows by select
         const bool bad = __builtin_amdgcn_ballot_w64(!__builtin_isfinite(S)) != 0;
-        full_p = (t + 16 <= s1) && (16 * R == K) && !bad;
-        tp = t;
+        full_p = rows == 16 && (16 * R == K) && !bad;
+        rowp = rowt;
+        rows_p = rows;
+        rowt += rowstep;
     }
     flush();
     // the ring's last DMAs (clamped tiles past the end) land before the
@@ -642,6 +710,8 @@ hipError_t launch_estep_resp_split(int variant, const float* ep, int Kp, int K, 
     const int64_t tiles = (n + 15) / 16;
     const int64_t blocks = ((tiles < resident_waves ? tiles : resident_waves) + wpb - 1) / wpb;
     const int64_t waves = blocks * wpb;
+    // the kernel steps its addresses by 16 waves samples held in 32 bits
+    if (waves >= (int64_t)1 << 26) return hipErrorInvalidValue;
 #define X(RR, WW, OO)                                                                                          \
     if (R == RR && wpb == WW && occ == OO) {                                                                   \
         hipLaunchKernelGGL((estep_resp_split_kernel<RR, WW, OO>), dim3((unsigned)blocks), dim3(64 * WW), 0, st, ep, \

@@ -709,6 +709,35 @@ int sdmm_learned_load_json(const char* path, int cap, int* C_out, int* M_out, fl
  * value = eval (ESolidAngle).  pdf: the solid-angle pdf of wo. */
 int sdmm_bsdf_phong_host(const float* params, const float rho[3], const float wi[3], const float* u, float wo[3],
                          float value[3], float* pdf);
+/* RoughDielectric::sample / eval / pdf (bsdfs/roughdielectric.cpp: eval
+ * :317-395, pdf :397-469, sample(bRec, pdf, sample) :560-662; isotropic
+ * Beckmann, sampleVisible = false, ERadiance) on the host, as the device Li
+ * runs them, with the semantics of sdmm_bsdf_phong_host: params = the 8
+ * bsdf_params floats of a kind-4 BSDF, spec_trans its specularTransmittance,
+ * wi the local incident direction (wi.z < 0: a hit from inside; wi.z == 0
+ * gives 0).  With u (3 uniforms: the microfacet normal's two, then the lobe
+ * choice that the reference draws with bRec.sampler->next1D(), reflection
+ * when u[2] <= F): wo is sampled (out), value = sample's return value (0 with
+ * pdf 0 for a void sample: microfacet pdf 0, a failed side check, cosThetaT ==
+ * 0) and *eta_out = bRec.eta, the relative index the sample crossed (1 on
+ * reflection, eta entering, 1 / eta leaving; 1 for a void sample).  u NULL:
+ * wo is given (either side), value = eval (ESolidAngle), and *eta_out what
+ * sample would have set for that wo: 1 if wi.z * wo.z > 0, else eta for wi.z
+ * > 0 and 1 / eta for wi.z < 0 -- the library's reading for a guide-chosen
+ * direction, where the reference multiplies the path's eta by a bRec.eta that
+ * BSDFSamplingRecord's constructor never initialises (records.inl:24-27).
+ * pdf: the solid-angle pdf of wo.  Inputs and outputs are floats; between
+ * them the arithmetic is double (the float32 formulas miss their float64
+ * values by 1e-4 .. 2e-3 where they cancel: DESIGN.md section 10). */
+int sdmm_bsdf_roughdielectric_host(const float* params, const float spec_trans[3], const float wi[3], const float* u,
+                                   float wo[3], float value[3], float* pdf, float* eta_out);
+/* The same over nq queries on device planes (SoA), asynchronous on
+ * hip_stream, each query bitwise the host call's: wi[3] the incident planes;
+ * u[3] the uniforms' planes (sample mode: wo[3] is written) or NULL (eval
+ * mode: wo[3] is read); value[3], pdf and eta_out planes of nq floats. */
+int sdmm_bsdf_roughdielectric_device(const float* params, const float spec_trans[3], int64_t nq,
+                                     const float* const wi[3], const float* const* u, float* const wo[3],
+                                     float* const value[3], float* pdf, float* eta_out, void* hip_stream);
 typedef struct {
     int n_quads;
     const float* quads;
@@ -738,7 +767,17 @@ typedef struct {
      * modified Phong (bsdfs/phong.cpp; its diffuseReflectance in
      * `reflectance`, both reflectances after configure()'s energy scaling):
      * [1..3] specularReflectance, [4] exponent, [5] the specular sampling
-     * weight sAvg / (dAvg + sAvg) (phong.cpp:146-148), [6], [7] unused. */
+     * weight sAvg / (dAvg + sAvg) (phong.cpp:146-148), [6], [7] unused.
+     * Kind 4, rough dielectric (bsdfs/roughdielectric.cpp; its
+     * specularTransmittance in `reflectance`): [1..3] specularReflectance,
+     * [4] eta = intIOR / extIOR (> 0 and != 1), [5] 1 / eta, [6] the Beckmann
+     * alpha (isotropic, sampleVisible = false), [7] unused.  Its quads are
+     * two-sided: a path meeting one from behind is inside the medium, the
+     * BSDF runs in Frame(n) of the stored normal, the saved vertex carries -n
+     * (sdmm_proc.cpp:765-767), and the path's relative index (Russian
+     * roulette, :864) is multiplied by the index each bounce crossed -- for a
+     * guide-chosen direction by what sample would have set for it (see
+     * sdmm_bsdf_roughdielectric_host). */
     const float* bsdf_params;
     /* nullable: n_bsdfs entries (appended in round 6) -- a rough conductor's
      * learned BSDF, the material's SDMM4 (roughconductor.cpp:182-194,
@@ -748,9 +787,12 @@ typedef struct {
     const struct sdmm_learned_bsdf4* learned_models;
     /* nullable: n_bsdfs entries (appended after learned_models; the
      * zero-initialise rule below covers older callers) -- the learned BSDFs
-     * over a C-dimensional condition.  Only Phong BSDFs (kind 3) read theirs:
-     * the material's SDMM5 (phong.cpp:75-90, :102-117), C = 3 and M >= 2 (the
-     * forced diffuse component is index 1); M = 0 (or the array NULL): none. */
+     * over a C-dimensional condition.  Phong BSDFs (kind 3) read theirs: the
+     * material's SDMM5 (phong.cpp:75-90, :102-117), C = 3 and M >= 2 (the
+     * forced diffuse component is index 1); so do rough dielectrics (kind 4):
+     * the SDMM5 over (theta_i, alpha, eta) (roughdielectric.cpp:198-211), C =
+     * 3 and M >= 1, conditioned on hits from outside only.  M = 0 (or the
+     * array NULL): none. */
     const struct sdmm_learned_bsdf* learned_models_nd;
 } sdmm_scene_desc;
 /* The descriptor has grown across ABI revisions (bsdf_params was appended):
@@ -780,7 +822,10 @@ typedef struct {
      * with a conductor or a Phong BSDF in the scene.  A Phong BSDF likewise
      * conditions its SDMM5 (sdmm_scene_desc.learned_models_nd: getDMM on
      * theta_i, the largest specular channel and log max(1, exponent), pruned
-     * to 2 with the diffuse component 1 forced, phong.cpp:75-90).  0: the plain
+     * to 2 with the diffuse component 1 forced, phong.cpp:75-90), and a rough
+     * dielectric its SDMM5 on (theta_i, alpha, eta), pruned to 2, for hits
+     * from outside (roughdielectric.cpp:198-211; from inside, without a model
+     * or a valid conditional: the plain conditional, h 0.5).  0: the plain
      * conditional with bsdf_fraction.  (bsdfOnly never trains, :416, so it
      * is the guided = 0 render; its learned-BSDF branch, :331/:384/:410, is
      * unreachable in the reference.) */

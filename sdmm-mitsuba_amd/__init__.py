@@ -196,6 +196,10 @@ def lib():
         L.sdmm_learned_load_json.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                              C.c_void_p, C.c_void_p]
         L.sdmm_bsdf_phong_host.argtypes = [C.c_void_p] * 7
+        L.sdmm_bsdf_roughdielectric_host.argtypes = [C.c_void_p] * 8
+        L.sdmm_bsdf_roughdielectric_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p * 3, C.c_void_p,
+                                                       C.c_void_p * 3, C.c_void_p * 3, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
         L.sdmm_stree_publish.argtypes = [C.c_void_p, C.c_void_p]
         L.sdmm_guide_ctx_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.sdmm_guide_ctx_destroy.argtypes = [C.c_void_p]
@@ -267,6 +271,7 @@ EXPORTED_SYMBOLS = [
     "sdmm_learned4_conditional_device",
     "sdmm_learned_conditional", "sdmm_learned_conditional_device", "sdmm_learned_save_json",
     "sdmm_learned_load_json", "sdmm_bsdf_phong_host",
+    "sdmm_bsdf_roughdielectric_host", "sdmm_bsdf_roughdielectric_device",
 ]
 
 
@@ -1405,6 +1410,56 @@ def bsdf_phong_host(params, rho, wi, u=None, wo=None):
                                       None if uu is None else uu.ctypes.data, out.ctypes.data, value.ctypes.data,
                                       C.cast(C.byref(pdf), C.c_void_p)))
     return out, value, float(np.float32(pdf.value))
+
+
+def bsdf_roughdielectric_host(params, spec_trans, wi, u=None, wo=None):
+    """RoughDielectric::sample (u given, 3 uniforms: (wo, weight, pdf, eta))
+    or eval / pdf of a given wo ((wo, eval, pdf, eta)) on the host
+    (sdmm_bsdf_roughdielectric_host), local frame; eta: the relative index the
+    direction crosses."""
+    params = np.ascontiguousarray(params, np.float32)
+    st = np.ascontiguousarray(spec_trans, np.float32)
+    wi = np.ascontiguousarray(wi, np.float32)
+    out = np.zeros(3, np.float32) if wo is None else np.array(wo, np.float32)
+    uu = None if u is None else np.ascontiguousarray(u, np.float32)
+    if uu is not None and uu.size != 3:
+        raise SDMMError("u: 3 uniforms expected")
+    value = np.zeros(3, np.float32)
+    pdf, eta = C.c_float(), C.c_float()
+    _check(lib().sdmm_bsdf_roughdielectric_host(params.ctypes.data, st.ctypes.data, wi.ctypes.data,
+                                                None if uu is None else uu.ctypes.data, out.ctypes.data,
+                                                value.ctypes.data, C.cast(C.byref(pdf), C.c_void_p),
+                                                C.cast(C.byref(eta), C.c_void_p)))
+    return out, value, float(np.float32(pdf.value)), float(np.float32(eta.value))
+
+
+def bsdf_roughdielectric_device(params, spec_trans, wi, u=None, wo=None, stream=None):
+    """sdmm_bsdf_roughdielectric_device over device planes: wi (3 float32
+    tensors of nq), u (3 tensors: sample mode) or wo (3 tensors: eval mode).
+    (wo[3], value[3], pdf, eta) device tensors; each query bitwise the host
+    call's."""
+    import torch
+    params = np.ascontiguousarray(params, np.float32)
+    st = np.ascontiguousarray(spec_trans, np.float32)
+    nq = wi[0].numel()
+    dev = wi[0].device
+    if (u is None) == (wo is None):
+        raise SDMMError("give either u (sample) or wo (eval)")
+    for t in list(wi) + list(u if u is not None else wo):
+        if t.numel() != nq or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise SDMMError("planes: contiguous float32 device tensors of one value per query")
+    out = [torch.empty(nq, device=dev) for _ in range(3)] if wo is None else list(wo)
+    value = [torch.empty(nq, device=dev) for _ in range(3)]
+    pdf = torch.empty(nq, device=dev)
+    eta = torch.empty(nq, device=dev)
+    up = None if u is None else (C.c_void_p * 3)(*[t.data_ptr() for t in u])
+    s_ = torch.cuda.current_stream(dev) if stream is None else stream
+    _check(lib().sdmm_bsdf_roughdielectric_device(
+        params.ctypes.data, st.ctypes.data, nq, (C.c_void_p * 3)(*[t.data_ptr() for t in wi]),
+        None if up is None else C.cast(up, C.c_void_p), (C.c_void_p * 3)(*[t.data_ptr() for t in out]),
+        (C.c_void_p * 3)(*[t.data_ptr() for t in value]), pdf.data_ptr(), eta.data_ptr(),
+        C.c_void_p(int(s_.cuda_stream) or None)))
+    return out, value, pdf, eta
 
 
 class _LiParams(C.Structure):

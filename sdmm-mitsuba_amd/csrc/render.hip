@@ -22,7 +22,9 @@
 // Scene: parallelograms (Mitsuba rectangles; a cube is six), diffuse BSDFs
 // (diffuse.cpp: cosine-hemisphere sampling, f = rho / pi) and smooth plastic
 // (plastic.cpp: a delta specular lobe with the dielectric Fresnel reflectance
-// over a diffuse base, the lobe chosen by Fresnel-weighted probability), one-
+// over a diffuse base, the lobe chosen by Fresnel-weighted probability), rough
+// conductors, Phong BSDFs (bsdf_phong.h) and rough dielectrics
+// (bsdf_roughdielectric.h: the one two-sided, transmitting material), one-
 // sided area emitters (area.cpp: Le = radiance on the normal side).  No NEE (the plugin's
 // NEE block is compiled out, :700-734; emitterPdf = 0, MIS weight 1, :811-816).
 //
@@ -34,6 +36,8 @@
 #include "render_device.h"
 #include "learned_bsdf.h"
 #include "bsdf_phong.h"
+#include "bsdf_beckmann.h"
+#include "bsdf_roughdielectric.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -45,9 +49,8 @@ namespace sdmm {
 constexpr float kEpsilon = 1e-4f;          // Mitsuba single-precision Epsilon (ray mint)
 constexpr float kInvPi = 0.31830988618379067154f;
 
-__device__ __forceinline__ float dot3(const float a[3], const float b[3]) {
-    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-}
+// dot3, normalize3 and the Beckmann distribution (beckmann_d, beckmann_g1,
+// beckmann_sample_all): bsdf_beckmann.h
 
 // closest hit with t in (mint, maxt); -1: none
 __device__ __forceinline__ int intersect(const SceneDev& S, const float o[3], const float d[3], float mint,
@@ -101,10 +104,8 @@ __device__ __forceinline__ float plastic_prob_specular(float Fi, float ssw) {
 // Beckmann distribution with isotropic alpha, sampleVisible = false (sampleAll
 // / pdfAll, microfacet.h:287-407 -- a documented choice of the plugin), a gray
 // conductor (eta, k equal over the channels; fresnelConductorExact's Spectrum
-// form, libcore/util.cpp:739-761) times the specular reflectance.  exp / log /
-// sin / cos as (float)f((double)x): math::fastexp / fastlog on Linux x86_64
-// (math.h:185-197) and the library's sincos convention.
-constexpr float kPiF = 3.14159265358979323846f;
+// form, libcore/util.cpp:739-761) times the specular reflectance.  The
+// distribution itself: bsdf_beckmann.h.
 
 __device__ __forceinline__ float fresnel_conductor(float ci, float eta, float k) {
     const float ci2 = ci * ci, si2 = 1.0f - ci2, si4 = si2 * si2;
@@ -118,52 +119,14 @@ __device__ __forceinline__ float fresnel_conductor(float ci, float eta, float k)
     return 0.5f * (rp2 + rs2);
 }
 
-// MicrofacetDistribution::eval (microfacet.h:191-233), Beckmann
-__device__ __forceinline__ float beckmann_d(const float m[3], float alpha) {
-    if (m[2] <= 0.0f) return 0.0f;
-    const float ct2 = m[2] * m[2];
-    const float ex = ((m[0] * m[0]) / (alpha * alpha) + (m[1] * m[1]) / (alpha * alpha)) / ct2;
-    float r = (float)exp((double)-ex) / (kPiF * alpha * alpha * ct2 * ct2);
-    if (r * m[2] < 1e-20f) r = 0.0f;
-    return r;
-}
-
-// smithG1 (microfacet.h:477-518), Beckmann's rational approximation
-__device__ __forceinline__ float beckmann_g1(const float v[3], const float m[3], float alpha) {
-    if (dot3(v, m) * v[2] <= 0.0f) return 0.0f;
-    const float tmp = 1.0f - v[2] * v[2];
-    const float tan_t = tmp <= 0.0f ? 0.0f : fabsf(sqrtf(tmp) / v[2]);
-    if (tan_t == 0.0f) return 1.0f;
-    const float a = 1.0f / (alpha * tan_t);
-    if (a >= 1.6f) return 1.0f;
-    const float a2 = a * a;
-    return (3.535f * a + 2.181f * a2) / (1.0f + 2.276f * a + 2.577f * a2);
-}
-
-// Vector3 normalize (v * (1 / |v|), vector.h:625-627)
-__device__ __forceinline__ void normalize3(const float v[3], float r[3]) {
-    const float rc = 1.0f / sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    r[0] = v[0] * rc; r[1] = v[1] * rc; r[2] = v[2] * rc;
-}
-
 // RoughConductor::sample(bRec, pdf, sample) (roughconductor.cpp:414-462) in the
 // local frame, wi.z > 0: wo, the weight F * (D G (wi.m) / (pdf cos)) and the
 // solid-angle pdf; false: the sample is void (weight 0)
 __device__ __forceinline__ bool conductor_sample(const float wi[3], const float* bp, float u0, float u1,
                                                  float wo[3], float bw[3], float* pdf) {
     const float alpha = bp[6];
-    // sampleAll (microfacet.h:287-395), isotropic Beckmann
-    const float phi = (2.0f * kPiF) * u1;
-    double sd, cd;
-    sincos((double)phi, &sd, &cd);
-    const float sp = (float)sd, cp = (float)cd;
-    const float a2 = alpha * alpha;
-    const float tan2 = a2 * -(float)log((double)(1.0f - u0));
-    const float ct = 1.0f / sqrtf(1.0f + tan2);
-    float mpdf = (1.0f - u0) / (kPiF * alpha * alpha * ct * ct * ct);
-    if (mpdf < 1e-20f) mpdf = 0.0f;
-    const float st = sqrtf(fmaxf(0.0f, 1.0f - ct * ct));
-    const float m[3] = {st * cp, st * sp, ct};
+    float m[3];
+    const float mpdf = beckmann_sample_all(alpha, u0, u1, m);
     *pdf = 0.0f;
     bw[0] = bw[1] = bw[2] = 0.0f;
     wo[0] = 0.0f; wo[1] = 0.0f; wo[2] = 1.0f;
@@ -261,12 +224,15 @@ li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) 
 // leaves (m_iteration != 0, :311-316); otherwise every query is BSDF only.
 // PHONG: the variant for a scene with Phong BSDFs (the three Li kernels carry
 // Phong's code only there, so the other scenes' kernels keep their registers).
-template <bool PHONG>
+// DIEL: likewise for a scene with rough dielectrics (bsdf_roughdielectric.h):
+// two-sided hits, the transmitted lobe and the path's relative index eta.
+template <bool PHONG, bool DIEL>
 __global__ void __launch_bounds__(256)
 li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int max_depth, int guided,
                 float h, uint64_t seed) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.P) return;
+    if (DIEL && bounce == 0) P.eta[i] = 1.0f;   // Float eta = 1.0f (sdmm_proc.cpp:604)
     int depth = P.depth[i];
     bool live = depth >= 0;
     if (live && max_depth >= 0 && depth >= max_depth) live = false;   // :684-685
@@ -283,7 +249,11 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         const bool zero_diff = kind == kBsdfConductor || (rho[0] == 0.0f && rho[1] == 0.0f && rho[2] == 0.0f);
         // no reflection from the back side or with zero reflectances (the
         // light's BSDF): sample and eval are 0, the path ends (:772-774)
-        if (!(dot3(wi, n) > 0.0f) || (zero_diff && zero_spec)) live = false;
+        // (a rough dielectric is live from either side: it dies only at
+        // wi . n == 0 or with both its reflectance and transmittance zero)
+        const float cos_i = dot3(wi, n);
+        const bool side = DIEL && kind == kBsdfDielectric ? (cos_i > 0.0f || cos_i < 0.0f) : cos_i > 0.0f;
+        if (!side || (zero_diff && zero_spec)) live = false;
     }
     Q.live[i] = (uint8_t)((live && guided) ? 1 : 0);
     Q.slot[i] = -1;
@@ -345,6 +315,18 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         phong_sample(wl, bp, rho, rng_uniform(seed, gp, stream, 0), rng_uniform(seed, gp, stream, 1), w, bw, &bpdf);
         Q.bw0[i] = bw[0]; Q.bw1[i] = bw[1]; Q.bw2[i] = bw[2];
         Q.bpdf[i] = bpdf;
+    } else if (DIEL && bp && bp[0] == (float)kBsdfDielectric) {
+        // RoughDielectric::sample (roughdielectric.cpp:560-662) in Frame(n)
+        // of the stored normal, whatever the side; the lobe choice (the
+        // reference's sampler->next1D()) is dimension 7
+        const float* st = S.refl + 3 * S.quads[q].bsdf;
+        const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};
+        float bw[3], bpdf, crossed;
+        roughdielectric_sample(wl, bp, st, rng_uniform(seed, gp, stream, 0), rng_uniform(seed, gp, stream, 1),
+                               rng_uniform(seed, gp, stream, 7), w, bw, &bpdf, &crossed);
+        Q.bw0[i] = bw[0]; Q.bw1[i] = bw[1]; Q.bw2[i] = bw[2];
+        Q.bpdf[i] = bpdf;
+        Q.beta[i] = crossed;
     } else {
         cosine_hemisphere(rng_uniform(seed, gp, stream, 0), rng_uniform(seed, gp, stream, 1), w);
     }
@@ -367,7 +349,7 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
 // bsdfs/diffuse.cpp:86-92; a rough conductor or a Phong BSDF: the query's own
 // row of the extended table, its learned model conditioned here) and the
 // BSDF/guide draw.
-template <bool PHONG>
+template <bool PHONG, bool DIEL>
 __global__ void __launch_bounds__(256)
 li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict__ count, int product) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -428,6 +410,25 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
             }
             for (int l = kept; l < Q.lM; ++l) Q.lw[row * Q.lM + l] = 0.0f;   // (skipped lobes)
             Q.k_mat[j] = kept > 0 ? (int32_t)row : -1;
+        } else if (DIEL && Q.lw && bp && bp[0] == (float)kBsdfDielectric) {
+            // RoughDielectric::getDMM (roughdielectric.cpp:198-211: the
+            // material's SDMM5 conditioned on (theta_i, alpha, eta), pruned to
+            // 2, no forced lobe) + rotate_to_wo, into the query's row as for
+            // the conductor; a hit from inside (cosTheta(wi) <= 0, :199), no
+            // model or no valid conditional: the plain conditional
+            const float wi[3] = {-P.dx[i], -P.dy[i], -P.dz[i]};
+            const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, QD.n)};
+            const int64_t row = (int64_t)Q.lrow0 + j;
+            const float* lm = S.lmodel_nd ? S.lmodel_nd + (size_t)kLearnedNdStride * QD.bsdf : nullptr;
+            const int M = lm ? (int)lm[1] : 0;
+            int kept = 0;
+            if (M > 0 && wl[2] > 0.0f) {
+                const float x[3] = {(float)acos((double)fminf(1.0f, wl[2])), bp[6], bp[4]};
+                kept = learned_conditional<3>(lm + 2, M, x, wl, kLearnedKeep, -1, Q.lw + row * Q.lM,
+                                              Q.lm + row * Q.lM * 3, Q.lc + row * Q.lM * 4);
+            }
+            for (int l = kept; l < Q.lM; ++l) Q.lw[row * Q.lM + l] = 0.0f;   // (skipped lobes)
+            Q.k_mat[j] = kept > 0 ? (int32_t)row : -1;
         }
     }
 }
@@ -439,7 +440,7 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
 // The wavefront marks a query whose BSDF sample was chosen comp == -2 (valid
 // conditional) -- the plain bounce's pdf_mode and the product bounce's
 // choice <= h alike.
-template <bool PHONG>
+template <bool PHONG, bool DIEL>
 __global__ void __launch_bounds__(256)
 li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int rr_depth, float h,
                 uint64_t seed, int product) {
@@ -458,6 +459,8 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     float wo[3], weight[3], mis_pdf;
     const float* bp = S.bpar ? S.bpar + kBsdfParams * QD.bsdf : nullptr;
     bool cacheable = true;
+    float crossed = 1.0f;               // bRec.eta (DIEL)
+    bool inside = false;                // cosTheta(bRec.wi) < 0 (DIEL)
     if (bp && bp[0] == (float)kBsdfPlastic) {
         // smooth plastic (plastic.cpp): the loop head's sample (weight, pdf,
         // lobe) or the guide's direction under eval / pdf, the smooth part only
@@ -531,6 +534,38 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
             mis_pdf = bsdf_pdf > 0.0f ? h * bsdf_pdf + (1.0f - h) * Q.pdf[j] : 0.0f;
             for (int ch = 0; ch < 3; ++ch) weight[ch] = mis_pdf == 0.0f ? 0.0f : f[ch] * (1.0f / mis_pdf);
         }
+    } else if (DIEL && bp && bp[0] == (float)kBsdfDielectric) {
+        // rough dielectric: as the conductor, on the whole sphere -- the
+        // guide's direction may lie below the surface, and the relative index
+        // it crosses is what sample would have set for it (the reference's
+        // bRec.eta is uninitialised there, records.inl:24-27)
+        const float bw[3] = {Q.bw0[i], Q.bw1[i], Q.bw2[i]};
+        const float wi[3] = {-P.dx[i], -P.dy[i], -P.dz[i]};
+        inside = dot3(wi, n) < 0.0f;
+        if (!valid || comp == -2) {
+            wo[0] = Q.b0[i]; wo[1] = Q.b1[i]; wo[2] = Q.b2[i];
+            crossed = Q.beta[i];
+            const float bsdf_pdf = Q.bpdf[i];
+            if (!valid) {
+                mis_pdf = bsdf_pdf;
+                for (int ch = 0; ch < 3; ++ch) weight[ch] = bw[ch];
+            } else {
+                mis_pdf = bsdf_pdf > 0.0f ? h * bsdf_pdf + (1.0f - h) * Q.pdf[j] : 0.0f;
+                for (int ch = 0; ch < 3; ++ch) weight[ch] = mis_pdf == 0.0f ? 0.0f : (bw[ch] * bsdf_pdf) * (1.0f / mis_pdf);
+            }
+        } else {
+            wo[0] = Q.d0[j]; wo[1] = Q.d1[j]; wo[2] = Q.d2[j];
+            float s[3], t[3];
+            frame_of(n, s, t);
+            const float wil[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};
+            const float wol[3] = {dot3(wo, s), dot3(wo, t), dot3(wo, n)};
+            const bool zero = (wo[0] == 0.0f && wo[1] == 0.0f && wo[2] == 0.0f) || !__builtin_isfinite(wol[2]);
+            float f[3] = {0.0f, 0.0f, 0.0f};
+            const float bsdf_pdf = zero ? 0.0f : roughdielectric_eval_pdf(wil, wol, bp, rho, f);
+            crossed = roughdielectric_crossed_eta(wil, wol, bp);
+            mis_pdf = bsdf_pdf > 0.0f ? h * bsdf_pdf + (1.0f - h) * Q.pdf[j] : 0.0f;
+            for (int ch = 0; ch < 3; ++ch) weight[ch] = mis_pdf == 0.0f ? 0.0f : f[ch] * (1.0f / mis_pdf);
+        }
     } else if (!valid) {
         // BSDF only, h = 1 (:316-323, :392-405): weight = rho, pdf = bsdfPdf
         wo[0] = Q.b0[i]; wo[1] = Q.b1[i]; wo[2] = Q.b2[i];
@@ -589,14 +624,21 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         for (int a = 0; a < 3; ++a) {
             vrec(P, 7 + a, nv, i) = c[a];
             vrec(P, 10 + a, nv, i) = wo[a];
-            vrec(P, 13 + a, nv, i) = n[a];
+            // (inside a dielectric the vertex carries the inward normal, :765-767)
+            vrec(P, 13 + a, nv, i) = DIEL && inside ? -n[a] : n[a];
         }
         P.nv[i] = nv + 1;
     }
     // Russian roulette (:858-868)
     bool live = q >= 0;
+    float eta = 1.0f;                   // the path's relative index (:788)
+    if (DIEL) {
+        eta = P.eta[i] * crossed;
+        P.eta[i] = eta;
+    }
     if (depth >= rr_depth && live) {
-        const float qq = fminf(fmaxf(thr[0], fmaxf(thr[1], thr[2])), 0.95f);
+        const float tmax = fmaxf(thr[0], fmaxf(thr[1], thr[2]));
+        const float qq = fminf(DIEL ? tmax * eta * eta : tmax, 0.95f);   // (:864)
         if (rng_uniform(seed, (uint64_t)(path0 + i), 1u + (uint32_t)bounce, 6) >= qq) live = false;
         else for (int ch = 0; ch < 3; ++ch) thr[ch] /= qq;
     }
@@ -770,6 +812,10 @@ __global__ void produce_seg_kernel(const uint32_t* __restrict__ keys, int64_t n,
 // ---------------------------------------------------------------------------
 // host launchers
 static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+// the Li kernel variant of a scene: <PHONG, DIEL> by the BSDF kinds it holds
+#define LI_VARIANT(kernel, S)                                                        \
+    ((S).has_dielectric ? ((S).has_phong ? kernel<true, true> : kernel<false, true>) \
+                        : ((S).has_phong ? kernel<true, false> : kernel<false, false>))
 
 hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, int64_t path0, int spp, uint64_t seed,
                             hipStream_t st) {
@@ -778,8 +824,8 @@ hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, int64_t path0,
 }
 hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
                            int max_depth, int guided, float h, uint64_t seed, hipStream_t st) {
-    hipLaunchKernelGGL(S.has_phong ? li_query_kernel<true> : li_query_kernel<false>, grid_for(P.P), dim3(256), 0, st,
-                       S, P, Q, path0, bounce, max_depth, guided, h, seed);
+    hipLaunchKernelGGL(LI_VARIANT(li_query_kernel, S), grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce,
+                       max_depth, guided, h, seed);
     return hipGetLastError();
 }
 size_t li_select_temp_bytes(int64_t n) {
@@ -794,15 +840,15 @@ hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDe
     hipError_t e = hipcub::DeviceSelect::Flagged(temp, temp_bytes, hipcub::CountingInputIterator<int32_t>(0), Q.live,
                                                  Q.idx, count_dev, (int)n, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(S.has_phong ? li_compact_kernel<true> : li_compact_kernel<false>, grid_for(n), dim3(256), 0,
-                       st, S, P, Q, (const int32_t*)count_dev, product);
+    hipLaunchKernelGGL(LI_VARIANT(li_compact_kernel, S), grid_for(n), dim3(256), 0, st, S, P, Q,
+                       (const int32_t*)count_dev, product);
     return hipGetLastError();
 }
 
 hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
                            int rr_depth, float h, uint64_t seed, int product, hipStream_t st) {
-    hipLaunchKernelGGL(S.has_phong ? li_shade_kernel<true> : li_shade_kernel<false>, grid_for(P.P), dim3(256), 0, st,
-                       S, P, Q, path0, bounce, rr_depth, h, seed, product);
+    hipLaunchKernelGGL(LI_VARIANT(li_shade_kernel, S), grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce,
+                       rr_depth, h, seed, product);
     return hipGetLastError();
 }
 // getDMM + rotate_to_wo for a batch of local incident directions against one
@@ -900,6 +946,48 @@ hipError_t launch_learned_nd(int C, const float* rec, int M, const float* const*
     else
         hipLaunchKernelGGL(learned_nd_kernel<3>, grid_for(nq), dim3(256), 0, st, m, M, cond, nq, wl[0], wl[1], wl[2],
                            keep, force, rows, w, mean, cov, n);
+    return hipGetLastError();
+}
+
+// The rough dielectric BSDF over a batch of local incident directions
+// (sdmm_bsdf_roughdielectric_device): sample mode draws wo from (u0, u1, u2),
+// eval mode (u0 null) evaluates the given wo; each query as the host call
+struct DielectricArgs {
+    float bp[kBsdfParams];
+    float st[3];
+};
+__global__ void __launch_bounds__(256)
+roughdielectric_kernel(DielectricArgs A, int64_t nq, const float* __restrict__ wi0, const float* __restrict__ wi1,
+                       const float* __restrict__ wi2, const float* __restrict__ u0, const float* __restrict__ u1,
+                       const float* __restrict__ u2, float* wo0, float* wo1, float* wo2, float* __restrict__ v0,
+                       float* __restrict__ v1, float* __restrict__ v2, float* __restrict__ pdf,
+                       float* __restrict__ eta_out) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const float wi[3] = {wi0[q], wi1[q], wi2[q]};
+    float wo[3], f[3], p, e;
+    if (u0) {
+        roughdielectric_sample(wi, A.bp, A.st, u0[q], u1[q], u2[q], wo, f, &p, &e);
+        wo0[q] = wo[0]; wo1[q] = wo[1]; wo2[q] = wo[2];
+    } else {
+        wo[0] = wo0[q]; wo[1] = wo1[q]; wo[2] = wo2[q];
+        p = roughdielectric_eval_pdf(wi, wo, A.bp, A.st, f);
+        e = roughdielectric_crossed_eta(wi, wo, A.bp);
+    }
+    v0[q] = f[0]; v1[q] = f[1]; v2[q] = f[2];
+    pdf[q] = p;
+    eta_out[q] = e;
+}
+hipError_t launch_roughdielectric(const float* bp, const float st[3], int64_t nq, const float* const wi[3],
+                                  const float* const* u, float* const wo[3], float* const value[3], float* pdf,
+                                  float* eta_out, hipStream_t st_) {
+    if (nq <= 0) return hipSuccess;
+    DielectricArgs A{};
+    for (int i = 0; i < kBsdfParams; ++i) A.bp[i] = bp[i];
+    for (int i = 0; i < 3; ++i) A.st[i] = st[i];
+    hipLaunchKernelGGL(roughdielectric_kernel, grid_for(nq), dim3(256), 0, st_, A, nq, wi[0], wi[1], wi[2],
+                       u ? u[0] : nullptr, u ? u[1] : nullptr, u ? u[2] : nullptr, wo[0], wo[1], wo[2], value[0],
+                       value[1], value[2], pdf, eta_out);
     return hipGetLastError();
 }
 

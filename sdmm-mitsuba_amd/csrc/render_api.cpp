@@ -17,6 +17,7 @@
 #include "render_device.h"
 #include "learned_bsdf.h"
 #include "bsdf_phong.h"
+#include "bsdf_roughdielectric.h"
 
 // the scene's derived quad data in plain IEEE float (no FMA contraction), as
 // the CPU restatement of Li forms it (oracle/sdmm_oracle_li.inc)
@@ -34,6 +35,9 @@ hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDe
                              void* temp, size_t temp_bytes, int product, hipStream_t st);
 hipError_t launch_li_film(const PathsDev& P, int64_t pix0, int64_t npix, int spp, int64_t plane, float* image,
                           float* image_sqr, hipStream_t st);
+hipError_t launch_roughdielectric(const float* bp, const float st[3], int64_t nq, const float* const wi[3],
+                                  const float* const* u, float* const wo[3], float* const value[3], float* pdf,
+                                  float* eta_out, hipStream_t st_);
 hipError_t launch_learned4(const float* rec, int M, float alpha, int64_t nq, const float* const wl[3], int keep,
                            float* w, float* mean, float* cov, int32_t* n, hipStream_t st);
 hipError_t launch_learned_nd(int C, const float* rec, int M, const float* const* rest, const float* scal, int64_t nq,
@@ -102,6 +106,7 @@ float dot3h(const float a[3], const float b[3]) { return a[0] * b[0] + a[1] * b[
 // path + query + vertex planes for P paths with V vertex slots
 int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
     if (P <= s->cap_paths && V <= s->cap_v && s->buf) return SDMM_OK;
+    const bool diel = s->S.has_dielectric != 0;   // (the eta planes: only with a rough dielectric)
     const int64_t cap = std::max<int64_t>(P, s->cap_paths);
     const int cv = std::max(V, s->cap_v);
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
@@ -111,7 +116,7 @@ int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
     (void)hipcub::DeviceReduce::Sum(nullptr, tb, (const int32_t*)nullptr, (int64_t*)nullptr, (int)cap);
     tb = std::max(tb, li_select_temp_bytes(cap));
     const size_t need = 12 * f + 4 * i4 + recb + 13 * f + u1 + i4 + 256 + al(tb) + 9 * f + 2 * u1 + 3 * i4 +
-                        (1 + 1 + 9 + 1) * f + i4 + u1 + 4 * f;
+                        (1 + 1 + 9 + 1) * f + i4 + u1 + 4 * f + (diel ? 2 * f : 0);
     HIP_TRY(hipStreamSynchronize(st));
     if (s->buf) HIP_TRY(hipFree(s->buf));
     s->buf = nullptr;
@@ -153,6 +158,8 @@ int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
     s->Q.bdelta = (uint8_t*)take(u1);
     float** bf[4] = {&s->Q.bw0, &s->Q.bw1, &s->Q.bw2, &s->Q.bpdf};
     for (float** q : bf) *q = (float*)take(f);
+    s->P.eta = diel ? (float*)take(f) : nullptr;
+    s->Q.beta = diel ? (float*)take(f) : nullptr;
     return SDMM_OK;
 }
 
@@ -223,7 +230,11 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
                              bp[5] >= 0.0f && std::isfinite(bp[5]) && bp[6] > 0.0f && bp[6] <= 2.0f) ||
                             (bp[0] == (float)kBsdfPhong && bp[1] >= 0.0f && bp[2] >= 0.0f && bp[3] >= 0.0f &&
                              std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] >= 0.0f && std::isfinite(bp[4]) &&
-                             bp[5] >= 0.0f && bp[5] <= 1.0f);
+                             bp[5] >= 0.0f && bp[5] <= 1.0f) ||
+                            (bp[0] == (float)kBsdfDielectric && bp[1] >= 0.0f && bp[2] >= 0.0f && bp[3] >= 0.0f &&
+                             std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] > 0.0f && bp[4] != 1.0f &&
+                             std::isfinite(bp[4]) && bp[5] > 0.0f && std::isfinite(bp[5]) && bp[6] > 0.0f &&
+                             bp[6] <= 2.0f);
             if (!ok) return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid bsdf_params");
         }
     // learned models: at most kLearnedMaxComp components, finite, unit directions
@@ -252,7 +263,8 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
         }
     }
     // learned models over a C-dimensional condition: the same checks; a Phong
-    // BSDF's is its SDMM5 with the forced diffuse component 1
+    // BSDF's is its SDMM5 with the forced diffuse component 1, a rough
+    // dielectric's its SDMM5 over (theta_i, alpha, eta)
     std::vector<float> lmod_nd;
     if (d->learned_models_nd) {
         lmod_nd.assign((size_t)kLearnedNdStride * (size_t)d->n_bsdfs, 0.0f);
@@ -264,6 +276,9 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
             const bool phong = d->bsdf_params && d->bsdf_params[kBsdfParams * b] == (float)kBsdfPhong;
             if (phong && (L.C != 3 || L.M <= kPhongDiffuseComponent))
                 return fail(SDMM_E_INVALID, "sdmm_scene_create: a Phong BSDF's learned model needs C = 3 and M >= 2");
+            const bool diel = d->bsdf_params && d->bsdf_params[kBsdfParams * b] == (float)kBsdfDielectric;
+            if (diel && L.C != 3)
+                return fail(SDMM_E_INVALID, "sdmm_scene_create: a rough dielectric's learned model needs C = 3");
             const int R = learned_rec(L.C), nm = L.C + 3, nc = (L.C + 2) * (L.C + 2);
             float* o = lmod_nd.data() + (size_t)kLearnedNdStride * b;
             o[0] = (float)L.C;
@@ -321,7 +336,8 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     if (d->bsdf_params)
         for (int q = 0; q < d->n_quads; ++q)
             if (d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfConductor ||
-                d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfPhong)
+                d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfPhong ||
+                d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfDielectric)
                 s->per_query_lobes = true;
     // render() (volpath_sdmm.cpp:375-393): spatialNormalization = the largest
     // extent; the tree box getAABB (:314-332)
@@ -365,8 +381,10 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     S.lmodel = s->dlmod;
     S.lmodel_nd = s->dlmod_nd;
     if (d->bsdf_params)
-        for (int b = 0; b < d->n_bsdfs; ++b)
+        for (int b = 0; b < d->n_bsdfs; ++b) {
             if (d->bsdf_params[kBsdfParams * b] == (float)kBsdfPhong) S.has_phong = 1;
+            if (d->bsdf_params[kBsdfParams * b] == (float)kBsdfDielectric) S.has_dielectric = 1;
+        }
     S.rad = s->drad;
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 4; ++c) S.cam[4 * r + c] = d->camera_to_world[4 * r + c];
@@ -513,6 +531,37 @@ int sdmm_bsdf_phong_host(const float* params, const float rho[3], const float wi
         *pdf = phong_eval_pdf(wi, wo, params, rho, value);
     }
     _mm_setcsr(csr);
+    return SDMM_OK;
+}
+
+int sdmm_bsdf_roughdielectric_host(const float* params, const float spec_trans[3], const float wi[3], const float* u,
+                                   float wo[3], float value[3], float* pdf, float* eta_out) {
+    if (!params || params[0] != (float)kBsdfDielectric || !spec_trans || !wi || !wo || !value || !pdf || !eta_out)
+        return fail(SDMM_E_INVALID, "sdmm_bsdf_roughdielectric_host: invalid argument (params of a kind-4 BSDF)");
+    const unsigned csr = _mm_getcsr();
+    _mm_setcsr(csr | 0x8040u);
+    if (u) {
+        float o[3];
+        roughdielectric_sample(wi, params, spec_trans, u[0], u[1], u[2], o, value, pdf, eta_out);
+        for (int a = 0; a < 3; ++a) wo[a] = o[a];
+    } else {
+        *pdf = roughdielectric_eval_pdf(wi, wo, params, spec_trans, value);
+        *eta_out = roughdielectric_crossed_eta(wi, wo, params);
+    }
+    _mm_setcsr(csr);
+    return SDMM_OK;
+}
+
+int sdmm_bsdf_roughdielectric_device(const float* params, const float spec_trans[3], int64_t nq,
+                                     const float* const wi[3], const float* const* u, float* const wo[3],
+                                     float* const value[3], float* pdf, float* eta_out, void* hip_stream) {
+    if (!params || params[0] != (float)kBsdfDielectric || !spec_trans || nq < 0)
+        return fail(SDMM_E_INVALID, "sdmm_bsdf_roughdielectric_device: invalid argument (params of a kind-4 BSDF)");
+    if (nq == 0) return SDMM_OK;
+    if (!wi || !wi[0] || !wi[1] || !wi[2] || !wo || !wo[0] || !wo[1] || !wo[2] || !value || !value[0] ||
+        !value[1] || !value[2] || !pdf || !eta_out || (u && (!u[0] || !u[1] || !u[2])))
+        return fail(SDMM_E_INVALID, "sdmm_bsdf_roughdielectric_device: NULL plane");
+    HIP_TRY(launch_roughdielectric(params, spec_trans, nq, wi, u, wo, value, pdf, eta_out, (hipStream_t)hip_stream));
     return SDMM_OK;
 }
 

@@ -19,7 +19,8 @@ __host__ __device__ __forceinline__ float rng_uniform(uint64_t seed, uint64_t pa
     return (float)(uint32_t)(k >> 40) * (1.0f / 16777216.0f);
 }
 // streams: 0 camera; 1 + b bounce b (dims: 0-1 BSDF sample, 2 BSDF/guide
-// choice, 3-5 guide sample, 6 roulette); kJitterStream + d: vertex d's jitters
+// choice, 3-5 guide sample, 6 roulette, 7 a rough dielectric's lobe choice);
+// kJitterStream + d: vertex d's jitters
 constexpr uint32_t kJitterStream = 1024;
 
 constexpr int kVertexFields = 16;          // weight 3, throughput 3, pdf, point 6, normal 3
@@ -32,7 +33,8 @@ struct QuadDev {
 };
 
 // Per-BSDF parameters beside the diffuse reflectance (kBsdfParams floats per
-// BSDF): [0] kind (0 diffuse, 1 smooth plastic, 2 rough conductor, 3 Phong).
+// BSDF): [0] kind (0 diffuse, 1 smooth plastic, 2 rough conductor, 3 Phong, 4
+// rough dielectric).
 // Plastic: [1..3] specular reflectance, [4] eta = intIOR / extIOR, [5] 1 /
 // eta^2, [6] the internal diffuse Fresnel reflectance fdrInt, [7] the
 // specular sampling weight sAvg / (dAvg + sAvg) (bsdfs/plastic.cpp:159-200).
@@ -40,11 +42,15 @@ struct QuadDev {
 // conductor), [6] the Beckmann alpha, [7] unused (bsdfs/roughconductor.cpp).
 // Phong: [1..3] specular reflectance, [4] exponent, [5] the specular sampling
 // weight sAvg / (dAvg + sAvg), [6], [7] unused (bsdfs/phong.cpp:129-156).
+// Rough dielectric: [1..3] specular reflectance, [4] eta = intIOR / extIOR,
+// [5] 1 / eta, [6] the Beckmann alpha, [7] unused; its specularTransmittance
+// in the BSDF's reflectance row (bsdfs/roughdielectric.cpp:213-241).
 constexpr int kBsdfParams = 8;
 constexpr int kBsdfDiffuse = 0;
 constexpr int kBsdfPlastic = 1;
 constexpr int kBsdfConductor = 2;
 constexpr int kBsdfPhong = 3;
+constexpr int kBsdfDielectric = 4;
 
 struct SceneDev {
     const QuadDev* quads;
@@ -59,6 +65,7 @@ struct SceneDev {
     int width, height;
     float smin[3], snorm;
     int has_phong;        // some BSDF is Phong: the Li kernels' PHONG variants run
+    int has_dielectric;   // some BSDF is a rough dielectric: their DIEL variants run
 };
 
 struct PathsDev {
@@ -73,6 +80,7 @@ struct PathsDev {
     float* rec;              // vertex records: rec[(f * V + v) * P + p]
     int V;
     int64_t P;
+    float* eta;              // the path's relative index (sdmm_proc.cpp:788); null without a rough dielectric
 };
 
 struct QueryDev {
@@ -102,7 +110,9 @@ struct QueryDev {
     // sampled lobe delta (1) or smooth (0), its weight (RGB) and pdf
     uint8_t* bdelta;
     float *bw0, *bw1, *bw2, *bpdf;
-    // product with a rough conductor's or a Phong BSDF's learned model:
+    float* beta;             // a rough dielectric's sample: the index it crossed (bRec.eta); null without one
+    // product with a rough conductor's, a Phong BSDF's or a rough
+    // dielectric's learned model:
     // compact query j's lobes (weights, local means, covariances) at row
     // lrow0 + j of the render's extended learned-BSDF table (lM lobes a row);
     // lw null: no such material

@@ -176,6 +176,26 @@ def phong_params(diffuse_rgb, specular_rgb=(0.2, 0.2, 0.2), exponent=30.0):
     return np.array([3.0, *sp, exponent, ssw, 0.0, 0.0], f32), d
 
 
+def dielectric_params(specular_rgb=(1.0, 1.0, 1.0), transmittance_rgb=(1.0, 1.0, 1.0), int_ior=1.5046,
+                      ext_ior=1.000277, alpha=0.1):
+    """(the 8 bsdf_params floats of a rough dielectric, its
+    specularTransmittance -- the BSDF's `reflectance` row)
+    (bsdfs/roughdielectric.cpp:213-241; include/sdmm_gpu.h sdmm_scene_desc):
+    kind 4, specularReflectance, eta = intIOR / extIOR (bk7 / air, the
+    plugin's defaults) and 1 / eta in float, the isotropic Beckmann alpha
+    (sampleVisible = false).  Both spectra must lie in [0, 1]
+    (ensureEnergyConservation would rescale them otherwise)."""
+    f32 = np.float32
+    sp, tr = np.asarray(specular_rgb, f32), np.asarray(transmittance_rgb, f32)
+    if sp.min() < 0 or sp.max() > 1 or tr.min() < 0 or tr.max() > 1:
+        raise ValueError("specular reflectance / transmittance outside [0, 1]")
+    if not (int_ior > 0 and ext_ior > 0 and int_ior != ext_ior):
+        raise ValueError("the interior and exterior indices of refraction must be positive and differ")
+    eta = f32(f32(int_ior) / f32(ext_ior))
+    inv_eta = f32(f32(1.0) / eta)
+    return np.array([4.0, *sp, eta, inv_eta, alpha, 0.0], f32), tr
+
+
 LEARNED_CONDUCTOR = Path(__file__).resolve().parent / "data" / "conductor_beckmann_4c.sdmm4.json"
 
 
@@ -194,6 +214,9 @@ def load_learned(path=LEARNED_CONDUCTOR):
 LEARNED_PHONG = Path(__file__).resolve().parent / "data" / "phong_4c.sdmm5.json"
 
 
+LEARNED_DIELECTRIC = Path(__file__).resolve().parent / "data" / "dielectric_4c.sdmm5.json"
+
+
 def load_learned_nd(path=LEARNED_PHONG):
     """A learned BSDF over a C-dimensional condition (sdmm-amd.sdmm5 JSON,
     include/sdmm_gpu.h sdmm_learned_load_json; an sdmm-amd.sdmm4 file is C =
@@ -210,7 +233,9 @@ def load_learned_nd(path=LEARNED_PHONG):
 
 
 def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, learned=LEARNED_CONDUCTOR, phong=(),
-                phong_learned=LEARNED_PHONG, phong_specular=(0.4, 0.4, 0.4), phong_exponent=30.0):
+                phong_learned=LEARNED_PHONG, phong_specular=(0.4, 0.4, 0.4), phong_exponent=30.0, dielectric=(),
+                dielectric_learned=LEARNED_DIELECTRIC, dielectric_alpha=0.1, dielectric_ior=(1.5046, 1.000277),
+                dielectric_specular=(1.0, 1.0, 1.0), dielectric_transmittance=(1.0, 1.0, 1.0), dielectric_lift=0.0):
     """sdmm_scene_desc fields for the Cornell Box (numpy arrays).  plastic:
     names of BSDFs (e.g. "TallBox", "ShortBox", "Floor") rendered as smooth
     plastic over their diffuse reflectance (a delta specular lobe beside a
@@ -223,14 +248,24 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
     phong: names rendered as Phong BSDFs (the Kitchen's most common learned
     material) over their diffuse reflectance with phong_specular /
     phong_exponent, each with the learned SDMM5 `phong_learned` (None: no
-    model) -- the stand-in of tools/make_learned_phong.py by default."""
+    model) -- the stand-in of tools/make_learned_phong.py by default.
+    dielectric: names rendered as rough dielectrics (the Kitchen's
+    `roughdielectric` glass) with dielectric_specular / _transmittance /
+    _alpha / _ior = (intIOR, extIOR), each with the learned SDMM5
+    `dielectric_learned` (None: no model) -- the stand-in of
+    tools/make_learned_dielectric.py by default.  dielectric_lift raises a
+    dielectric cube by that much along y: the cubes stand on the floor, and a
+    glass box's bottom face would be coplanar with it."""
     names = list(_BSDFS)
     quads, bsdf, flip, emitter = [], [], [], []
     for m, name, fl in _RECTS:
         quads.append(np.concatenate(_rect(_mat(m))))
         bsdf.append(names.index(name)); flip.append(int(fl)); emitter.append(-1)
     for m, name in _CUBES:
-        for f in _cube_faces(_mat(m)):
+        M = _mat(m)
+        if name in dielectric:
+            M[1, 3] += dielectric_lift
+        for f in _cube_faces(M):
             quads.append(np.concatenate(f))
             bsdf.append(names.index(name)); flip.append(0); emitter.append(-1)
     quads.append(np.concatenate(_rect(_mat(_LIGHT))))
@@ -238,10 +273,10 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
     cam = np.array([float(x) for x in _CAMERA.split()], np.float32)
     extra = {}
     refl = {n: _BSDFS[n] for n in names}
-    if plastic or conductor or phong:
-        kinds = [set(plastic), set(conductor), set(phong)]
+    if plastic or conductor or phong or dielectric:
+        kinds = [set(plastic), set(conductor), set(phong), set(dielectric)]
         unknown = set().union(*kinds) - set(names)
-        twice = (kinds[0] & kinds[1]) | (kinds[0] & kinds[2]) | (kinds[1] & kinds[2])
+        twice = {n for n in names if sum(n in k for k in kinds) > 1}
         if unknown or twice:
             raise ValueError(f"unknown or doubly assigned BSDFs {sorted(unknown | twice)}")
         bp = np.zeros((len(names), 8), np.float32)
@@ -252,6 +287,9 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
                 bp[i] = conductor_params(tuple(min(1.0, 1.25 * c) for c in _BSDFS[nm]), alpha=alpha)
             elif nm in phong:
                 bp[i], refl[nm] = phong_params(_BSDFS[nm], phong_specular, phong_exponent)
+            elif nm in dielectric:
+                bp[i], refl[nm] = dielectric_params(dielectric_specular, dielectric_transmittance, *dielectric_ior,
+                                                    alpha=dielectric_alpha)
         extra["bsdf_params"] = bp.reshape(-1)
         if conductor and learned is not None:
             model = load_learned(learned)
@@ -259,6 +297,10 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
         if phong and phong_learned is not None:
             model = load_learned_nd(phong_learned)
             extra["learned_models_nd"] = [model if nm in phong else None for nm in names]
+        if dielectric and dielectric_learned is not None:
+            model = load_learned_nd(dielectric_learned)
+            nd = extra.setdefault("learned_models_nd", [None] * len(names))
+            extra["learned_models_nd"] = [model if nm in dielectric else cur for nm, cur in zip(names, nd)]
     return {**extra,
         "quads": np.asarray(quads, np.float32).reshape(-1),
         "flip_normals": np.asarray(flip, np.int32),

@@ -574,7 +574,8 @@ int sdmm_restore_params(sdmm_mix* m, const sdmm_params_out* in);
 int sdmm_stree_set_nodes(sdmm_stree* t, int n, const float* aabb, const int32_t* child, const int32_t* axis);
 
 /* ---- Guided path tracing on the device (SDMMRenderer::Li) ----------------
- * An analytic scene of parallelograms (Mitsuba rectangles; a cube is six) with
+ * An analytic scene of parallelograms (Mitsuba rectangles; a cube is six) and
+ * an optional triangle mesh (sdmm_scene_desc's mesh fields; face normals) with
  * diffuse BSDFs and one-sided area emitters, rendered by a wavefront path
  * tracer whose every bounce goes through sdmm_guide_pdf_wavefront -- the
  * plugin's per-bounce sampleSurface / pdfSurface (sdmm_proc.cpp:275-590,
@@ -794,6 +795,37 @@ typedef struct {
      * 3 and M >= 1, conditioned on hits from outside only.  M = 0 (or the
      * array NULL): none. */
     const struct sdmm_learned_bsdf* learned_models_nd;
+    /* A triangle mesh beside the quads (appended after learned_models_nd; the
+     * zero-initialise rule below covers older callers: n_triangles = 0 and
+     * every rule above holds, the other mesh fields are then not read).
+     *   mesh_vertices     3 floats per vertex in world space (the caller
+     *                     applies toWorld), n_mesh_vertices of them
+     *   triangles         3 vertex indices per triangle, n_triangles of them
+     *   tri_bsdf          required with triangles: indexes the same BSDF
+     *                     tables as bsdf[q]; any kind, the two-sided 4 included
+     *   tri_emitter       nullable, -1 = none: indexes radiance, one-sided as
+     *                     for quads (radiance and n_emitters are required
+     *                     when it is set, also without a quad `emitter`)
+     *   tri_flip_normals  nullable
+     * The normal is the face normal normalize((p1 - p0) x (p2 - p0)), negated
+     * where flipped.  Vertex and shading normals, UVs, textures and
+     * instancing are not supported.  n_quads may be 0 with triangles.
+     * Primitive ids: quads 0 .. n_quads-1, triangle i is n_quads + i; the
+     * learned-BSDF row of a hit is still its bsdf index, and the scene AABB
+     * of sdmm_scene_normalization includes every mesh vertex.
+     * SDMM_E_INVALID (with a message): a vertex index out of range, a
+     * non-finite vertex, a zero-area triangle (cross product of length 0 in
+     * float), a material or emitter index out of range, more than 2^26
+     * triangles, a BVH deeper than the traversal stack (24 inner levels: what
+     * a median-split tree of 2^26 triangles needs, so a valid mesh always
+     * fits). */
+    int n_mesh_vertices;
+    const float* mesh_vertices;
+    int n_triangles;
+    const int32_t* triangles;
+    const int32_t* tri_bsdf;
+    const int32_t* tri_emitter;
+    const int32_t* tri_flip_normals;
 } sdmm_scene_desc;
 /* The descriptor has grown across ABI revisions (bsdf_params was appended):
  * zero-initialise it (`sdmm_scene_desc d = {0};` / `memset`) before filling
@@ -856,6 +888,38 @@ int sdmm_scene_normalization(const sdmm_scene* s, float scene_min[3], float* spa
                              float tree_max[3]);
 int sdmm_li_render(sdmm_scene* s, sdmm_stree* t, const sdmm_mix* const* node_mix, const sdmm_li_params* p,
                    float* image, float* image_sqr, sdmm_path_vertices* vertices_out, sdmm_li_stats* stats);
+/* The closest hit of nq rays against the scene's quads and triangles, as the
+ * Li kernels find it: o, d three device planes each (origin, direction; the
+ * direction need not be unit), prim[nq] the hit's primitive id or -1, t[nq]
+ * its distance (maxt without a hit).  Asynchronous on hip_stream.
+ * The closest-hit rule: t in (mint, maxt), the smallest t wins, on exactly
+ * equal t the lowest primitive id.  mode 0 walks the triangles' BVH (built
+ * on the host at sdmm_scene_create: binned SAH, leaves of at most 4, 64-byte
+ * nodes holding both children's boxes; the walk visits every subtree whose
+ * entry distance is not greater than the current best, so ties are seen),
+ * mode 1 loops over all triangles with the same triangle test
+ * (Triangle::rayIntersect, core/triangle.h:109-145); the quads go through
+ * their loop in both.  Both modes, here and on the host, are meant to return
+ * bitwise the same (prim, t): the walk's cull carries a measured margin (1e-4
+ * relative) against the triangle test's rounding, so this is tested on the
+ * suite's rays and meshes, not proven for every input. */
+int sdmm_scene_intersect(const sdmm_scene* s, int64_t nq, const float* const o[3], const float* const d[3], float mint,
+                         float maxt, int mode, int32_t* prim, float* t, void* hip_stream);
+/* The same entirely on the host (no HIP call: runs without a GPU) from a
+ * description -- o, d host arrays [nq][3]; camera and film fields are not
+ * read.  Validates as sdmm_scene_create does, builds the same BVH and walks
+ * it with the same traversal source. */
+int sdmm_scene_intersect_host(const sdmm_scene_desc* desc, int64_t nq, const float* o, const float* d, float mint,
+                              float maxt, int mode, int32_t* prim, float* t);
+/* Debug view of the BVH built for desc's mesh (host only).  max_levels: the
+ * cap on inner levels (0: the traversal stack's 24; a smaller cap forces
+ * median splits, and SDMM_E_INVALID when even those do not fit).  *n_nodes,
+ * *levels (nullable) always; with cap_nodes >= *n_nodes also boxes[n][2][2][3]
+ * (child, lo / hi, axis), children[n][2] (>= 0 an inner node, < 0 a leaf: ~c
+ * = first * 8 + count into the leaf order) and order[n_triangles] (leaf order
+ * -> triangle index).  cap_nodes 0: a size query. */
+int sdmm_mesh_bvh_dump(const sdmm_scene_desc* desc, int max_levels, int* n_nodes, int* levels, int cap_nodes,
+                       float* boxes, int32_t* children, int32_t* order);
 
 /* Training-data producer: the tail of Li (sdmm_proc.cpp:876-965) for a batch
  * of paths' saved vertices.  Per path, vertices nv-1 down to

@@ -171,6 +171,12 @@ def lib():
         L.sdmm_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         L.sdmm_scene_destroy.argtypes = [C.c_void_p]
         L.sdmm_scene_normalization.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+        L.sdmm_scene_intersect.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sdmm_scene_intersect_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                                C.c_int, C.c_void_p, C.c_void_p]
+        L.sdmm_mesh_bvh_dump.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
         L.sdmm_li_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
         L.sdmm_write_exr.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float]
@@ -272,6 +278,7 @@ EXPORTED_SYMBOLS = [
     "sdmm_learned_conditional", "sdmm_learned_conditional_device", "sdmm_learned_save_json",
     "sdmm_learned_load_json", "sdmm_bsdf_phong_host",
     "sdmm_bsdf_roughdielectric_host", "sdmm_bsdf_roughdielectric_device",
+    "sdmm_scene_intersect", "sdmm_scene_intersect_host", "sdmm_mesh_bvh_dump",
 ]
 
 
@@ -1235,7 +1242,78 @@ class _SceneDesc(C.Structure):
                 ("n_bsdfs", C.c_int), ("reflectance", C.c_void_p), ("emitter", C.c_void_p),
                 ("n_emitters", C.c_int), ("radiance", C.c_void_p), ("camera_to_world", C.c_float * 16),
                 ("fov_x_deg", C.c_float), ("near_clip", C.c_float), ("width", C.c_int), ("height", C.c_int),
-                ("bsdf_params", C.c_void_p), ("learned_models", C.c_void_p), ("learned_models_nd", C.c_void_p)]
+                ("bsdf_params", C.c_void_p), ("learned_models", C.c_void_p), ("learned_models_nd", C.c_void_p),
+                ("n_mesh_vertices", C.c_int), ("mesh_vertices", C.c_void_p), ("n_triangles", C.c_int),
+                ("triangles", C.c_void_p), ("tri_bsdf", C.c_void_p), ("tri_emitter", C.c_void_p),
+                ("tri_flip_normals", C.c_void_p)]
+
+
+def _fill_geometry(d, desc, keep):
+    """The geometry and material fields of a _SceneDesc from a description
+    dict (numpy arrays; kept alive in `keep`): quads and the triangle mesh."""
+    def arr(key, dtype):
+        a = np.ascontiguousarray(desc[key], dtype)
+        keep[key] = a
+        return a
+    if "quads" in desc and np.asarray(desc["quads"]).size:
+        d.n_quads = arr("quads", np.float32).size // 9
+        d.quads = keep["quads"].ctypes.data
+        d.flip_normals = arr("flip_normals", np.int32).ctypes.data if "flip_normals" in desc else None
+        d.bsdf = arr("bsdf", np.int32).ctypes.data
+    refl = arr("reflectance", np.float32)
+    d.n_bsdfs = refl.size // 3
+    d.reflectance = refl.ctypes.data
+    if "emitter" in desc and d.n_quads:
+        d.emitter = arr("emitter", np.int32).ctypes.data
+    if "radiance" in desc:
+        d.n_emitters = arr("radiance", np.float32).size // 3
+        d.radiance = keep["radiance"].ctypes.data
+    if "triangles" in desc:
+        d.n_triangles = arr("triangles", np.int32).size // 3
+        d.triangles = keep["triangles"].ctypes.data
+    if "mesh_vertices" in desc:
+        d.n_mesh_vertices = arr("mesh_vertices", np.float32).size // 3
+        d.mesh_vertices = keep["mesh_vertices"].ctypes.data
+    for key in ("tri_bsdf", "tri_emitter", "tri_flip_normals"):
+        if desc.get(key) is not None:
+            setattr(d, key, arr(key, np.int32).ctypes.data)
+
+
+def intersect_host(desc, o, d, mint=1e-4, maxt=float("inf"), mode=0):
+    """sdmm_scene_intersect_host: the closest hit of rays o, d (numpy [nq, 3])
+    against a description's quads and triangles, entirely on the host (no
+    GPU).  mode 0: the BVH, 1: the loop over all triangles.  (prim int32[nq],
+    -1 = none; t float32[nq], maxt without a hit)."""
+    sd, keep = _SceneDesc(), {}
+    _fill_geometry(sd, desc, keep)
+    o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+    dd = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    if o.shape != dd.shape:
+        raise SDMMError("o and d: [nq, 3] each")
+    prim = np.empty(len(o), np.int32)
+    t = np.empty(len(o), np.float32)
+    _check(lib().sdmm_scene_intersect_host(C.byref(sd), len(o), o.ctypes.data, dd.ctypes.data, float(mint),
+                                           float(maxt), int(mode), prim.ctypes.data, t.ctypes.data))
+    return prim, t
+
+
+def mesh_bvh_dump(desc, max_levels=0):
+    """sdmm_mesh_bvh_dump: the BVH built for a description's mesh (host only)
+    as {"levels", "boxes" [n, 2, 2, 3] (child, lo / hi, axis), "children"
+    [n, 2] (>= 0 inner node, < 0 leaf: ~c = first * 8 + count), "order"
+    [n_triangles] (leaf order -> triangle index)}."""
+    sd, keep = _SceneDesc(), {}
+    _fill_geometry(sd, desc, keep)
+    n, lv = C.c_int(), C.c_int()
+    _check(lib().sdmm_mesh_bvh_dump(C.byref(sd), int(max_levels), C.cast(C.byref(n), C.c_void_p),
+                                    C.cast(C.byref(lv), C.c_void_p), 0, None, None, None))
+    boxes = np.empty((n.value, 2, 2, 3), np.float32)
+    children = np.empty((n.value, 2), np.int32)
+    order = np.empty(sd.n_triangles, np.int32)
+    _check(lib().sdmm_mesh_bvh_dump(C.byref(sd), int(max_levels), C.cast(C.byref(n), C.c_void_p),
+                                    C.cast(C.byref(lv), C.c_void_p), n.value, boxes.ctypes.data,
+                                    children.ctypes.data, order.ctypes.data))
+    return {"levels": lv.value, "boxes": boxes, "children": children, "order": order}
 
 
 class _Learned4(C.Structure):
@@ -1597,16 +1675,8 @@ class Scene:
     def __init__(self, desc: dict, device: int = 0):
         self._keep = {k: np.ascontiguousarray(v) for k, v in desc.items() if isinstance(v, np.ndarray)}
         d = _SceneDesc()
-        d.n_quads = self._keep["quads"].size // 9
-        d.quads = self._keep["quads"].ctypes.data
-        d.flip_normals = self._keep["flip_normals"].ctypes.data if "flip_normals" in self._keep else None
-        d.bsdf = self._keep["bsdf"].ctypes.data
-        d.n_bsdfs = self._keep["reflectance"].size // 3
-        d.reflectance = self._keep["reflectance"].ctypes.data
-        if "emitter" in self._keep:
-            d.emitter = self._keep["emitter"].ctypes.data
-            d.n_emitters = self._keep["radiance"].size // 3
-            d.radiance = self._keep["radiance"].ctypes.data
+        _fill_geometry(d, desc, self._keep)
+        self.n_quads, self.n_triangles = d.n_quads, d.n_triangles
         for i, v in enumerate(np.asarray(desc["camera_to_world"], np.float32).reshape(-1)):
             d.camera_to_world[i] = float(v)
         d.fov_x_deg = float(desc["fov_x_deg"])
@@ -1652,6 +1722,27 @@ class Scene:
         _check(lib().sdmm_scene_normalization(self.h, smin.ctypes.data, norm.ctypes.data, tmin.ctypes.data,
                                               tmax.ctypes.data))
         return smin, float(norm[0]), tmin, tmax
+
+    def intersect(self, o, d, mint=1e-4, maxt=float("inf"), mode=0, stream=None):
+        """sdmm_scene_intersect: the closest hit of rays on device planes --
+        o, d: 3 float32 device tensors of nq each.  mode 0: the triangles' BVH,
+        1: the loop over all triangles.  (prim int32[nq], -1 = none; t
+        float32[nq]) device tensors; every mode and intersect_host agree
+        bitwise."""
+        import torch
+        nq = o[0].numel()
+        dev = o[0].device
+        for t_ in list(o) + list(d):
+            if t_.numel() != nq or t_.dtype != torch.float32 or not t_.is_contiguous() or t_.device != dev:
+                raise SDMMError("planes: contiguous float32 device tensors of one value per ray")
+        prim = torch.empty(nq, device=dev, dtype=torch.int32)
+        t = torch.empty(nq, device=dev)
+        s_ = torch.cuda.current_stream(dev) if stream is None else stream
+        _check(lib().sdmm_scene_intersect(self.h, nq, C.cast((C.c_void_p * 3)(*[x.data_ptr() for x in o]), C.c_void_p),
+                                          C.cast((C.c_void_p * 3)(*[x.data_ptr() for x in d]), C.c_void_p),
+                                          float(mint), float(maxt), int(mode), prim.data_ptr(), t.data_ptr(),
+                                          C.c_void_p(int(s_.cuda_stream) or None)))
+        return prim, t
 
     def render(self, tree: "STree", node_mix=None, spp: int = 1, max_depth: int = 10, rr_depth: int = 10,
                guided: bool = False, bsdf_fraction: float = 0.5, saved_vertices: int = 9, seed: int = 0,

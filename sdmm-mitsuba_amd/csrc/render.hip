@@ -19,7 +19,9 @@
 // The camera kernel starts the paths (first hit, its emission: :641-677); the
 // film kernel averages each pixel's samples in sample order (box filter).
 //
-// Scene: parallelograms (Mitsuba rectangles; a cube is six), diffuse BSDFs
+// Scene: parallelograms (Mitsuba rectangles; a cube is six) and an optional
+// triangle mesh (face normals; its BVH walked by the MESH variants of the
+// camera and shade kernels: mesh_bvh.h), diffuse BSDFs
 // (diffuse.cpp: cosine-hemisphere sampling, f = rho / pi) and smooth plastic
 // (plastic.cpp: a delta specular lobe with the dielectric Fresnel reflectance
 // over a diffuse base, the lobe chosen by Fresnel-weighted probability), rough
@@ -52,27 +54,56 @@ constexpr float kInvPi = 0.31830988618379067154f;
 // dot3, normalize3 and the Beckmann distribution (beckmann_d, beckmann_g1,
 // beckmann_sample_all): bsdf_beckmann.h
 
-// closest hit with t in (mint, maxt); -1: none
+// closest hit with t in (mint, maxt); -1: none.  Quads by their loop
+// (quads_closest, render_device.h); MESH: then the triangles through the BVH
+// (mesh_bvh.h), its stack in LDS as [level][thread] -- stack points at this
+// thread's column, 256 apart.  Primitive id: a quad, or n_quads + triangle.
+struct LdsStack {
+    int* col;
+    __device__ __forceinline__ void push(int level, int node) { col[level * 256] = node; }
+    __device__ __forceinline__ int pop(int level) const { return col[level * 256]; }
+};
+template <bool MESH>
 __device__ __forceinline__ int intersect(const SceneDev& S, const float o[3], const float d[3], float mint,
-                                         float maxt, float& t_hit) {
-    int best = -1;
-    float tb = maxt;
-    for (int q = 0; q < S.n_quads; ++q) {
-        const QuadDev& Q = S.quads[q];
-        const float denom = dot3(d, Q.n);
-        if (denom == 0.0f) continue;
-        const float r0[3] = {Q.p0[0] - o[0], Q.p0[1] - o[1], Q.p0[2] - o[2]};
-        const float t = dot3(r0, Q.n) / denom;
-        if (!(t > mint && t < tb)) continue;
-        const float r[3] = {o[0] + t * d[0] - Q.p0[0], o[1] + t * d[1] - Q.p0[1], o[2] + t * d[2] - Q.p0[2]};
-        const float a = dot3(r, Q.g1), b = dot3(r, Q.g2);
-        if (a < 0.0f || a > 1.0f || b < 0.0f || b > 1.0f) continue;
-        tb = t;
-        best = q;
+                                         float maxt, float& t_hit, int* stack) {
+    int best = quads_closest(S.quads, S.n_quads, o, d, mint, maxt, t_hit);
+    if constexpr (MESH) {
+        if (S.mesh_brute) {
+            mesh_brute(S.tris, S.n_tris, S.n_quads, o, d, mint, maxt, best, t_hit);
+        } else {
+            LdsStack st{stack};
+            bvh_closest(S.nodes, S.tris, S.n_quads, o, d, mint, maxt, best, t_hit, st);
+        }
     }
-    t_hit = tb;
     return best;
 }
+// the hit primitive's normal, BSDF and emitter: a quad's fields, or (MESH, q
+// >= n_quads) the triangle's hit record
+template <bool MESH>
+__device__ __forceinline__ const float* prim_n(const SceneDev& S, int q) {
+    if constexpr (MESH)
+        if (q >= S.n_quads) return S.hits[q - S.n_quads].n;
+    return S.quads[q].n;
+}
+template <bool MESH>
+__device__ __forceinline__ int prim_bsdf(const SceneDev& S, int q) {
+    if constexpr (MESH)
+        if (q >= S.n_quads) return S.hits[q - S.n_quads].bsdf;
+    return S.quads[q].bsdf;
+}
+template <bool MESH>
+__device__ __forceinline__ int prim_emitter(const SceneDev& S, int q) {
+    if constexpr (MESH)
+        if (q >= S.n_quads) return S.hits[q - S.n_quads].emitter;
+    return S.quads[q].emitter;
+}
+// the MESH kernels' traversal stack: kBvhStack levels x 256 threads of LDS
+#define LI_MESH_STACK(stack)                              \
+    int* stack = nullptr;                                 \
+    if constexpr (MESH) {                                 \
+        __shared__ int bvh_lds[kBvhStack * 256];          \
+        stack = bvh_lds + threadIdx.x;                    \
+    }
 
 // Frame(n) (frame_of) and warp::squareToCosineHemisphere (cosine_hemisphere):
 // bsdf_phong.h
@@ -181,10 +212,12 @@ __device__ __forceinline__ void record_radiance(const PathsDev& P, int64_t p, in
 // ---------------------------------------------------------------------------
 // camera rays: pixel = path / spp (box filter, uniform jitter), Mitsuba's
 // perspective mapping (fov along x): local d = ((1 - 2 sx) tan, (1 - 2 sy) tan / aspect, 1)
+template <bool MESH>
 __global__ void __launch_bounds__(256)
 li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.P) return;
+    LI_MESH_STACK(stack)
     const int64_t gp = path0 + i;
     const int64_t pix = gp / spp;
     const int px = (int)(pix % S.width), py = (int)(pix / S.width);
@@ -201,18 +234,19 @@ li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) 
     const float dn = 1.0f / sqrtf(dot3(d, d));
     for (int a = 0; a < 3; ++a) d[a] *= dn;
     float t;
-    const int q = intersect(S, o, d, S.near_clip / l[2], INFINITY, t);
+    const int q = intersect<MESH>(S, o, d, S.near_clip / l[2], INFINITY, t, stack);
     P.tr[i] = 1.0f; P.tg[i] = 1.0f; P.tb[i] = 1.0f;
     P.nv[i] = 0;
     P.nray[i] = 0;
     P.dx[i] = d[0]; P.dy[i] = d[1]; P.dz[i] = d[2];
     float L[3] = {0.0f, 0.0f, 0.0f};
     if (q >= 0) {
-        const QuadDev& Q = S.quads[q];
+        const float* qn = prim_n<MESH>(S, q);
+        const int qe = prim_emitter<MESH>(S, q);
         P.px[i] = o[0] + t * d[0]; P.py[i] = o[1] + t * d[1]; P.pz[i] = o[2] + t * d[2];
         // emission seen directly (:674-677), before any vertex exists
-        if (Q.emitter >= 0 && -dot3(d, Q.n) > 0.0f)
-            for (int ch = 0; ch < 3; ++ch) L[ch] = S.rad[3 * Q.emitter + ch];
+        if (qe >= 0 && -dot3(d, qn) > 0.0f)
+            for (int ch = 0; ch < 3; ++ch) L[ch] = S.rad[3 * qe + ch];
     }
     P.lr[i] = L[0]; P.lg[i] = L[1]; P.lb[i] = L[2];
     P.quad[i] = q;
@@ -226,7 +260,7 @@ li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) 
 // Phong's code only there, so the other scenes' kernels keep their registers).
 // DIEL: likewise for a scene with rough dielectrics (bsdf_roughdielectric.h):
 // two-sided hits, the transmitted lobe and the path's relative index eta.
-template <bool PHONG, bool DIEL>
+template <bool PHONG, bool DIEL, bool MESH>
 __global__ void __launch_bounds__(256)
 li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int max_depth, int guided,
                 float h, uint64_t seed) {
@@ -239,11 +273,12 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     int q = live ? P.quad[i] : -1;
     float n[3] = {0, 0, 0}, wi[3] = {0, 0, 0};
     if (live) {
-        const QuadDev& QD = S.quads[q];
-        n[0] = QD.n[0]; n[1] = QD.n[1]; n[2] = QD.n[2];
+        const float* qn = prim_n<MESH>(S, q);
+        const int qb = prim_bsdf<MESH>(S, q);
+        n[0] = qn[0]; n[1] = qn[1]; n[2] = qn[2];
         wi[0] = -P.dx[i]; wi[1] = -P.dy[i]; wi[2] = -P.dz[i];
-        const float* rho = S.refl + 3 * QD.bsdf;
-        const float* bp = S.bpar ? S.bpar + kBsdfParams * QD.bsdf : nullptr;
+        const float* rho = S.refl + 3 * qb;
+        const float* bp = S.bpar ? S.bpar + kBsdfParams * qb : nullptr;
         const int kind = bp ? (int)bp[0] : kBsdfDiffuse;
         const bool zero_spec = kind == kBsdfDiffuse || (bp[1] == 0.0f && bp[2] == 0.0f && bp[3] == 0.0f);
         const bool zero_diff = kind == kBsdfConductor || (rho[0] == 0.0f && rho[1] == 0.0f && rho[2] == 0.0f);
@@ -269,14 +304,14 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     Q.c2[i] = (p[2] - S.smin[2]) / S.snorm;
     float s[3], t[3], w[3];
     frame_of(n, s, t);
-    const float* bp = S.bpar ? S.bpar + kBsdfParams * S.quads[q].bsdf : nullptr;
+    const float* bp = S.bpar ? S.bpar + kBsdfParams * prim_bsdf<MESH>(S, q) : nullptr;
     uint8_t delta = 0;
     if (bp && bp[0] == (float)kBsdfPlastic) {
         // SmoothPlastic::sample(bRec, pdf, sample) (plastic.cpp:378-420): the
         // delta mirror lobe with probability probSpecular, else the cosine
         // hemisphere on the rescaled first coordinate; weight and pdf for the
         // shade kernel (a mixture bounce keeps the sampled lobe, :392-407)
-        const float* rho = S.refl + 3 * S.quads[q].bsdf;
+        const float* rho = S.refl + 3 * prim_bsdf<MESH>(S, q);
         const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};   // Frame::toLocal
         const float Fi = fresnel_dielectric(wl[2], bp[4]);
         const float ps = plastic_prob_specular(Fi, bp[7]);
@@ -309,7 +344,7 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         Q.bpdf[i] = bpdf;
     } else if (PHONG && bp && bp[0] == (float)kBsdfPhong) {
         // Phong::sample (phong.cpp:232-289); a void sample has weight 0
-        const float* rho = S.refl + 3 * S.quads[q].bsdf;
+        const float* rho = S.refl + 3 * prim_bsdf<MESH>(S, q);
         const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};
         float bw[3], bpdf;
         phong_sample(wl, bp, rho, rng_uniform(seed, gp, stream, 0), rng_uniform(seed, gp, stream, 1), w, bw, &bpdf);
@@ -319,7 +354,7 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         // RoughDielectric::sample (roughdielectric.cpp:560-662) in Frame(n)
         // of the stored normal, whatever the side; the lobe choice (the
         // reference's sampler->next1D()) is dimension 7
-        const float* st = S.refl + 3 * S.quads[q].bsdf;
+        const float* st = S.refl + 3 * prim_bsdf<MESH>(S, q);
         const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};
         float bw[3], bpdf, crossed;
         roughdielectric_sample(wl, bp, st, rng_uniform(seed, gp, stream, 0), rng_uniform(seed, gp, stream, 1),
@@ -349,7 +384,7 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
 // bsdfs/diffuse.cpp:86-92; a rough conductor or a Phong BSDF: the query's own
 // row of the extended table, its learned model conditioned here) and the
 // BSDF/guide draw.
-template <bool PHONG, bool DIEL>
+template <bool PHONG, bool DIEL, bool MESH>
 __global__ void __launch_bounds__(256)
 li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict__ count, int product) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -361,17 +396,18 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
     Q.k_mode[j] = Q.mode[i];
     Q.slot[i] = j;
     if (product) {
-        const QuadDev& QD = S.quads[P.quad[i]];
+        const float* qn = prim_n<MESH>(S, P.quad[i]);
+        const int qb = prim_bsdf<MESH>(S, P.quad[i]);
         float s[3], t[3];
-        frame_of(QD.n, s, t);
+        frame_of(qn, s, t);
         for (int r = 0; r < 3; ++r) {
             Q.k_F[3 * r][j] = s[r];
             Q.k_F[3 * r + 1][j] = t[r];
-            Q.k_F[3 * r + 2][j] = QD.n[r];
+            Q.k_F[3 * r + 2][j] = qn[r];
         }
-        Q.k_mat[j] = QD.bsdf;
+        Q.k_mat[j] = qb;
         Q.k_ch[j] = Q.ch[i];
-        const float* bp = S.bpar ? S.bpar + kBsdfParams * QD.bsdf : nullptr;
+        const float* bp = S.bpar ? S.bpar + kBsdfParams * qb : nullptr;
         if (Q.lw && bp && bp[0] == (float)kBsdfConductor) {
             // getDMM (roughconductor.cpp:182-194: the material's SDMM4
             // conditioned on (theta_i, alpha), pruned to 2) + rotate_to_wo
@@ -379,9 +415,9 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
             // its row of the extended table; no model or no valid conditional:
             // no learned BSDF (the plain conditional, h 0.5)
             const float wi[3] = {-P.dx[i], -P.dy[i], -P.dz[i]};
-            const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, QD.n)};
+            const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, qn)};
             const int64_t row = (int64_t)Q.lrow0 + j;
-            const float* lm = S.lmodel ? S.lmodel + (size_t)kLearnedStride * QD.bsdf : nullptr;
+            const float* lm = S.lmodel ? S.lmodel + (size_t)kLearnedStride * qb : nullptr;
             const int M = lm ? (int)lm[0] : 0;
             int kept = 0;
             if (M > 0) {
@@ -397,9 +433,9 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
             // to 2 with the diffuse component forced) + rotate_to_wo, into the
             // query's row as for the conductor
             const float wi[3] = {-P.dx[i], -P.dy[i], -P.dz[i]};
-            const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, QD.n)};
+            const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, qn)};
             const int64_t row = (int64_t)Q.lrow0 + j;
-            const float* lm = S.lmodel_nd ? S.lmodel_nd + (size_t)kLearnedNdStride * QD.bsdf : nullptr;
+            const float* lm = S.lmodel_nd ? S.lmodel_nd + (size_t)kLearnedNdStride * qb : nullptr;
             const int M = lm ? (int)lm[1] : 0;
             int kept = 0;
             if (M > 0) {
@@ -417,9 +453,9 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
             // the conductor; a hit from inside (cosTheta(wi) <= 0, :199), no
             // model or no valid conditional: the plain conditional
             const float wi[3] = {-P.dx[i], -P.dy[i], -P.dz[i]};
-            const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, QD.n)};
+            const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, qn)};
             const int64_t row = (int64_t)Q.lrow0 + j;
-            const float* lm = S.lmodel_nd ? S.lmodel_nd + (size_t)kLearnedNdStride * QD.bsdf : nullptr;
+            const float* lm = S.lmodel_nd ? S.lmodel_nd + (size_t)kLearnedNdStride * qb : nullptr;
             const int M = lm ? (int)lm[1] : 0;
             int kept = 0;
             if (M > 0 && wl[2] > 0.0f) {
@@ -440,7 +476,7 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
 // The wavefront marks a query whose BSDF sample was chosen comp == -2 (valid
 // conditional) -- the plain bounce's pdf_mode and the product bounce's
 // choice <= h alike.
-template <bool PHONG, bool DIEL>
+template <bool PHONG, bool DIEL, bool MESH>
 __global__ void __launch_bounds__(256)
 li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int rr_depth, float h,
                 uint64_t seed, int product) {
@@ -448,16 +484,18 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     if (i >= P.P) return;
     int depth = P.depth[i];
     if (depth < 0) return;
-    const QuadDev& QD = S.quads[P.quad[i]];
-    const float n[3] = {QD.n[0], QD.n[1], QD.n[2]};
-    const float* rho = S.refl + 3 * QD.bsdf;
+    LI_MESH_STACK(stack)
+    const int pq = P.quad[i];
+    const float* qn = prim_n<MESH>(S, pq);
+    const float n[3] = {qn[0], qn[1], qn[2]};
+    const float* rho = S.refl + 3 * prim_bsdf<MESH>(S, pq);
     const float c[3] = {Q.c0[i], Q.c1[i], Q.c2[i]};
     const int j = Q.slot[i];            // the path's guided query (-1: none, BSDF only)
     const int comp = j >= 0 ? Q.comp[j] : -1;
     const bool valid = comp != -1;      // validConditional (:368)
     if (product && valid) h = Q.hq[j];
     float wo[3], weight[3], mis_pdf;
-    const float* bp = S.bpar ? S.bpar + kBsdfParams * QD.bsdf : nullptr;
+    const float* bp = S.bpar ? S.bpar + kBsdfParams * prim_bsdf<MESH>(S, pq) : nullptr;
     bool cacheable = true;
     float crossed = 1.0f;               // bRec.eta (DIEL)
     bool inside = false;                // cosTheta(bRec.wi) < 0 (DIEL)
@@ -501,7 +539,7 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
             const float rd = 1.0f / (1.0f - bp[6]);
             const float k = cpdf * bp[5] * (1.0f - Fi) * (1.0f - Fo);
             for (int ch = 0; ch < 3; ++ch) {
-                const float f = up ? S.refl[3 * QD.bsdf + ch] * rd * k : 0.0f;
+                const float f = up ? S.refl[3 * prim_bsdf<MESH>(S, pq) + ch] * rd * k : 0.0f;
                 weight[ch] = mis_pdf == 0.0f ? 0.0f : f * (1.0f / mis_pdf);
             }
         }
@@ -598,12 +636,12 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     // trace and look for an emitter (rayIntersectAndLookForEmitter)
     const float o[3] = {P.px[i], P.py[i], P.pz[i]};
     float t;
-    const int q = intersect(S, o, wo, kEpsilon, INFINITY, t);
+    const int q = intersect<MESH>(S, o, wo, kEpsilon, INFINITY, t, stack);
     float value[3] = {0.0f, 0.0f, 0.0f};
     if (q >= 0) {
-        const QuadDev& H = S.quads[q];
-        if (H.emitter >= 0 && -dot3(wo, H.n) > 0.0f)
-            for (int ch = 0; ch < 3; ++ch) value[ch] = S.rad[3 * H.emitter + ch];
+        const int he = prim_emitter<MESH>(S, q);
+        if (he >= 0 && -dot3(wo, prim_n<MESH>(S, q)) > 0.0f)
+            for (int ch = 0; ch < 3; ++ch) value[ch] = S.rad[3 * he + ch];
     }
     int nv = P.nv[i];
     if (value[0] != 0.0f || value[1] != 0.0f || value[2] != 0.0f) {
@@ -813,13 +851,15 @@ __global__ void produce_seg_kernel(const uint32_t* __restrict__ keys, int64_t n,
 // host launchers
 static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 // the Li kernel variant of a scene: <PHONG, DIEL> by the BSDF kinds it holds
-#define LI_VARIANT(kernel, S)                                                        \
-    ((S).has_dielectric ? ((S).has_phong ? kernel<true, true> : kernel<false, true>) \
-                        : ((S).has_phong ? kernel<true, false> : kernel<false, false>))
+#define LI_VARIANT_M(kernel, S, M)                                                         \
+    ((S).has_dielectric ? ((S).has_phong ? kernel<true, true, M> : kernel<false, true, M>) \
+                        : ((S).has_phong ? kernel<true, false, M> : kernel<false, false, M>))
+#define LI_VARIANT(kernel, S) ((S).has_mesh ? LI_VARIANT_M(kernel, S, true) : LI_VARIANT_M(kernel, S, false))
 
 hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, int64_t path0, int spp, uint64_t seed,
                             hipStream_t st) {
-    hipLaunchKernelGGL(li_camera_kernel, grid_for(P.P), dim3(256), 0, st, S, P, path0, spp, seed);
+    hipLaunchKernelGGL((S.has_mesh ? li_camera_kernel<true> : li_camera_kernel<false>), grid_for(P.P), dim3(256), 0, st,
+                       S, P, path0, spp, seed);
     return hipGetLastError();
 }
 hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
@@ -988,6 +1028,43 @@ hipError_t launch_roughdielectric(const float* bp, const float st[3], int64_t nq
     hipLaunchKernelGGL(roughdielectric_kernel, grid_for(nq), dim3(256), 0, st_, A, nq, wi[0], wi[1], wi[2],
                        u ? u[0] : nullptr, u ? u[1] : nullptr, u ? u[2] : nullptr, wo[0], wo[1], wo[2], value[0],
                        value[1], value[2], pdf, eta_out);
+    return hipGetLastError();
+}
+
+// sdmm_scene_intersect: the closest hit of nq rays on device planes, quads by
+// their loop, then the triangles through the BVH (BRUTE: the loop over all)
+template <bool BRUTE>
+__global__ void __launch_bounds__(256)
+scene_intersect_kernel(SceneDev S, int64_t nq, const float* __restrict__ o0, const float* __restrict__ o1,
+                       const float* __restrict__ o2, const float* __restrict__ d0, const float* __restrict__ d1,
+                       const float* __restrict__ d2, float mint, float maxt, int32_t* __restrict__ prim,
+                       float* __restrict__ t_out) {
+    __shared__ int bvh_lds[BRUTE ? 1 : kBvhStack * 256];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const float o[3] = {o0[i], o1[i], o2[i]}, d[3] = {d0[i], d1[i], d2[i]};
+    float t;
+    int best = quads_closest(S.quads, S.n_quads, o, d, mint, maxt, t);
+    if (S.n_tris > 0) {
+        if (BRUTE) {
+            mesh_brute(S.tris, S.n_tris, S.n_quads, o, d, mint, maxt, best, t);
+        } else {
+            LdsStack st{bvh_lds + threadIdx.x};
+            bvh_closest(S.nodes, S.tris, S.n_quads, o, d, mint, maxt, best, t, st);
+        }
+    }
+    prim[i] = best;
+    t_out[i] = t;
+}
+hipError_t launch_scene_intersect(const SceneDev& S, int64_t nq, const float* const o[3], const float* const d[3],
+                                  float mint, float maxt, int mode, int32_t* prim, float* t, hipStream_t st) {
+    if (nq <= 0) return hipSuccess;
+    if (mode == 0)
+        hipLaunchKernelGGL(scene_intersect_kernel<false>, grid_for(nq), dim3(256), 0, st, S, nq, o[0], o[1], o[2],
+                           d[0], d[1], d[2], mint, maxt, prim, t);
+    else
+        hipLaunchKernelGGL(scene_intersect_kernel<true>, grid_for(nq), dim3(256), 0, st, S, nq, o[0], o[1], o[2],
+                           d[0], d[1], d[2], mint, maxt, prim, t);
     return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
@@ -35,6 +36,8 @@ hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDe
                              void* temp, size_t temp_bytes, int product, hipStream_t st);
 hipError_t launch_li_film(const PathsDev& P, int64_t pix0, int64_t npix, int spp, int64_t plane, float* image,
                           float* image_sqr, hipStream_t st);
+hipError_t launch_scene_intersect(const SceneDev& S, int64_t nq, const float* const o[3], const float* const d[3],
+                                  float mint, float maxt, int mode, int32_t* prim, float* t, hipStream_t st);
 hipError_t launch_roughdielectric(const float* bp, const float st[3], int64_t nq, const float* const wi[3],
                                   const float* const* u, float* const wo[3], float* const value[3], float* pdf,
                                   float* eta_out, hipStream_t st_);
@@ -62,6 +65,9 @@ struct sdmm_scene {
     float* dlmod = nullptr;   // kLearnedStride per BSDF (learned_models), null: none
     float* dlmod_nd = nullptr;   // kLearnedNdStride per BSDF (learned_models_nd), null: none
     float* drad = nullptr;
+    BvhNode* dnodes = nullptr;   // the triangle mesh (mesh_bvh.h), null without one
+    MeshTri* dtris = nullptr;
+    MeshHit* dhits = nullptr;
     float smin[3] = {0, 0, 0}, snorm = 1.0f, tmin[3] = {0, 0, 0}, tmax[3] = {0, 0, 0};
     // per-render buffers (grown)
     void* buf = nullptr;
@@ -209,15 +215,82 @@ int extend_learned(sdmm_scene* s, const sdmm_bsdf_table& user, int64_t cap, hipS
     return SDMM_OK;
 }
 
+// the geometry and material arguments of a description (sdmm_scene_create
+// and the host intersect entry): some primitive, its arrays, a BSDF table
+bool geometry_args_ok(const sdmm_scene_desc* d) {
+    return d->n_quads >= 0 && d->n_triangles >= 0 && (d->n_quads > 0 || d->n_triangles > 0) &&
+           (d->n_quads == 0 || (d->quads && d->bsdf)) && d->n_bsdfs >= 1 && d->reflectance;
+}
+// some primitive may carry an emitter index (quads' or triangles' array set):
+// the radiance table is needed, uploaded and read then
+bool has_emitters(const sdmm_scene_desc* d) { return d->emitter || (d->n_triangles > 0 && d->tri_emitter); }
+
+// the quads' derived data (normal, duals) and their corners' AABB, after the
+// description's argument checks.  0, or the error code (message set).
+int prep_quads(const sdmm_scene_desc* d, const char* who, std::vector<QuadDev>* qs, float mn[3], float mx[3]) {
+    const std::string w(who);
+    if (!geometry_args_ok(d)) return fail(SDMM_E_INVALID, w + ": invalid description");
+    if (has_emitters(d) && (d->n_emitters < 1 || !d->radiance))
+        return fail(SDMM_E_INVALID, w + ": emitters without radiance");
+    qs->assign((size_t)d->n_quads, QuadDev{});
+    for (int q = 0; q < d->n_quads; ++q) {
+        QuadDev& Q = (*qs)[(size_t)q];
+        const float* v = d->quads + 9 * q;
+        for (int a = 0; a < 3; ++a) { Q.p0[a] = v[a]; Q.e1[a] = v[3 + a]; Q.e2[a] = v[6 + a]; }
+        float n[3];
+        cross3(Q.e1, Q.e2, n);
+        const float len = std::sqrt(dot3h(n, n));
+        if (!(len > 0.0f)) return fail(SDMM_E_INVALID, w + ": degenerate quad");
+        const float sg = (d->flip_normals && d->flip_normals[q]) ? -1.0f : 1.0f;
+        for (int a = 0; a < 3; ++a) Q.n[a] = sg * n[a] / len;
+        // duals: g1 . e1 = 1, g1 . e2 = 0 (g1 ~ e2 x n), likewise g2
+        float a1[3], a2[3];
+        cross3(Q.e2, n, a1);
+        cross3(n, Q.e1, a2);
+        const float s1 = dot3h(Q.e1, a1), s2 = dot3h(Q.e2, a2);
+        for (int a = 0; a < 3; ++a) { Q.g1[a] = a1[a] / s1; Q.g2[a] = a2[a] / s2; }
+        Q.bsdf = d->bsdf[q];
+        Q.emitter = d->emitter ? d->emitter[q] : -1;
+        if (Q.bsdf < 0 || Q.bsdf >= d->n_bsdfs || Q.emitter < -1 || (Q.emitter >= 0 && Q.emitter >= d->n_emitters))
+            return fail(SDMM_E_INVALID, w + ": material index out of range");
+        // scene AABB without the camera: the four corners
+        for (int c = 0; c < 4; ++c)
+            for (int a = 0; a < 3; ++a) {
+                const float x = Q.p0[a] + ((c & 1) ? Q.e1[a] : 0.0f) + ((c & 2) ? Q.e2[a] : 0.0f);
+                mn[a] = std::min(mn[a], x);
+                mx[a] = std::max(mx[a], x);
+            }
+    }
+    return SDMM_OK;
+}
+
+// the description's triangle mesh, validated and built (n_triangles > 0);
+// max_levels 0: the traversal stack's cap
+int prep_mesh(const sdmm_scene_desc* d, const char* who, int max_levels, MeshBvh* m) {
+    MeshInput in;
+    in.n_vertices = d->n_mesh_vertices;
+    in.vertices = d->mesh_vertices;
+    in.n_triangles = d->n_triangles;
+    in.triangles = d->triangles;
+    in.bsdf = d->tri_bsdf;
+    in.emitter = d->tri_emitter;
+    in.flip = d->tri_flip_normals;
+    in.n_bsdfs = d->n_bsdfs;
+    in.n_emitters = d->n_emitters;
+    std::string err;
+    if (!mesh_build(in, max_levels, m, &err)) return fail(SDMM_E_INVALID, std::string(who) + ": " + err);
+    return SDMM_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
-    if (!out || !d || d->n_quads < 1 || !d->quads || !d->bsdf || d->n_bsdfs < 1 || !d->reflectance ||
-        d->width < 1 || d->height < 1 || !(d->fov_x_deg > 0.0f && d->fov_x_deg < 180.0f))
+    if (!out || !d || !geometry_args_ok(d) || d->width < 1 || d->height < 1 ||
+        !(d->fov_x_deg > 0.0f && d->fov_x_deg < 180.0f))
         return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid description");
-    if (d->emitter && (d->n_emitters < 1 || !d->radiance))
+    if (has_emitters(d) && (d->n_emitters < 1 || !d->radiance))
         return fail(SDMM_E_INVALID, "sdmm_scene_create: emitters without radiance");
     if (d->bsdf_params)
         for (int b = 0; b < d->n_bsdfs; ++b) {
@@ -299,35 +372,19 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
         }
     }
     *out = nullptr;
-    std::vector<QuadDev> qs((size_t)d->n_quads);
+    std::vector<QuadDev> qs;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int q = 0; q < d->n_quads; ++q) {
-        QuadDev& Q = qs[(size_t)q];
-        const float* v = d->quads + 9 * q;
-        for (int a = 0; a < 3; ++a) { Q.p0[a] = v[a]; Q.e1[a] = v[3 + a]; Q.e2[a] = v[6 + a]; }
-        float n[3];
-        cross3(Q.e1, Q.e2, n);
-        const float len = std::sqrt(dot3h(n, n));
-        if (!(len > 0.0f)) return fail(SDMM_E_INVALID, "sdmm_scene_create: degenerate quad");
-        const float sg = (d->flip_normals && d->flip_normals[q]) ? -1.0f : 1.0f;
-        for (int a = 0; a < 3; ++a) Q.n[a] = sg * n[a] / len;
-        // duals: g1 . e1 = 1, g1 . e2 = 0 (g1 ~ e2 x n), likewise g2
-        float a1[3], a2[3];
-        cross3(Q.e2, n, a1);
-        cross3(n, Q.e1, a2);
-        const float s1 = dot3h(Q.e1, a1), s2 = dot3h(Q.e2, a2);
-        for (int a = 0; a < 3; ++a) { Q.g1[a] = a1[a] / s1; Q.g2[a] = a2[a] / s2; }
-        Q.bsdf = d->bsdf[q];
-        Q.emitter = d->emitter ? d->emitter[q] : -1;
-        if (Q.bsdf < 0 || Q.bsdf >= d->n_bsdfs || Q.emitter < -1 || (Q.emitter >= 0 && Q.emitter >= d->n_emitters))
-            return fail(SDMM_E_INVALID, "sdmm_scene_create: material index out of range");
-        // scene AABB without the camera: the four corners
-        for (int c = 0; c < 4; ++c)
-            for (int a = 0; a < 3; ++a) {
-                const float x = Q.p0[a] + ((c & 1) ? Q.e1[a] : 0.0f) + ((c & 2) ? Q.e2[a] : 0.0f);
-                mn[a] = std::min(mn[a], x);
-                mx[a] = std::max(mx[a], x);
-            }
+    int rc = prep_quads(d, "sdmm_scene_create", &qs, mn, mx);
+    if (rc) return rc;
+    // the triangle mesh: validated, its BVH built; the AABB takes its vertices in
+    MeshBvh mesh;
+    if (d->n_triangles > 0) {
+        rc = prep_mesh(d, "sdmm_scene_create", 0, &mesh);
+        if (rc) return rc;
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = std::min(mn[a], mesh.mn[a]);
+            mx[a] = std::max(mx[a], mesh.mx[a]);
+        }
     }
     sdmm_scene* s = new (std::nothrow) sdmm_scene();
     if (!s) return fail(SDMM_E_NOMEM, "out of host memory");
@@ -339,6 +396,12 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
                 d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfPhong ||
                 d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfDielectric)
                 s->per_query_lobes = true;
+    if (d->bsdf_params)
+        for (int i = 0; i < d->n_triangles; ++i) {
+            const float kind = d->bsdf_params[kBsdfParams * d->tri_bsdf[i]];
+            if (kind == (float)kBsdfConductor || kind == (float)kBsdfPhong || kind == (float)kBsdfDielectric)
+                s->per_query_lobes = true;
+        }
     // render() (volpath_sdmm.cpp:375-393): spatialNormalization = the largest
     // extent; the tree box getAABB (:314-332)
     float ext[3], norm = 0.0f;
@@ -350,9 +413,18 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     }
     s->snorm = norm;
     hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc(&s->dquads, sizeof(QuadDev) * qs.size());
+    if (e == hipSuccess) e = hipMalloc(&s->dquads, sizeof(QuadDev) * std::max<size_t>(qs.size(), 1));
+    if (e == hipSuccess && d->n_triangles > 0) e = hipMalloc(&s->dnodes, sizeof(BvhNode) * mesh.nodes.size());
+    if (e == hipSuccess && d->n_triangles > 0) e = hipMalloc(&s->dtris, sizeof(MeshTri) * mesh.tris.size());
+    if (e == hipSuccess && d->n_triangles > 0) e = hipMalloc(&s->dhits, sizeof(MeshHit) * mesh.hits.size());
+    if (e == hipSuccess && d->n_triangles > 0)
+        e = hipMemcpy(s->dnodes, mesh.nodes.data(), sizeof(BvhNode) * mesh.nodes.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && d->n_triangles > 0)
+        e = hipMemcpy(s->dtris, mesh.tris.data(), sizeof(MeshTri) * mesh.tris.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && d->n_triangles > 0)
+        e = hipMemcpy(s->dhits, mesh.hits.data(), sizeof(MeshHit) * mesh.hits.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc(&s->drefl, sizeof(float) * 3 * (size_t)d->n_bsdfs);
-    if (e == hipSuccess && d->emitter) e = hipMalloc(&s->drad, sizeof(float) * 3 * (size_t)d->n_emitters);
+    if (e == hipSuccess && has_emitters(d)) e = hipMalloc(&s->drad, sizeof(float) * 3 * (size_t)d->n_emitters);
     if (e == hipSuccess && d->bsdf_params)
         e = hipMalloc(&s->dbpar, sizeof(float) * kBsdfParams * (size_t)d->n_bsdfs);
     if (e == hipSuccess && d->bsdf_params)
@@ -364,10 +436,11 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     if (e == hipSuccess && !lmod_nd.empty()) e = hipMalloc(&s->dlmod_nd, sizeof(float) * lmod_nd.size());
     if (e == hipSuccess && !lmod_nd.empty())
         e = hipMemcpy(s->dlmod_nd, lmod_nd.data(), sizeof(float) * lmod_nd.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(s->dquads, qs.data(), sizeof(QuadDev) * qs.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !qs.empty())
+        e = hipMemcpy(s->dquads, qs.data(), sizeof(QuadDev) * qs.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess)
         e = hipMemcpy(s->drefl, d->reflectance, sizeof(float) * 3 * (size_t)d->n_bsdfs, hipMemcpyHostToDevice);
-    if (e == hipSuccess && d->emitter)
+    if (e == hipSuccess && has_emitters(d))
         e = hipMemcpy(s->drad, d->radiance, sizeof(float) * 3 * (size_t)d->n_emitters, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         sdmm_scene_destroy(s);
@@ -380,6 +453,16 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     S.bpar = s->dbpar;
     S.lmodel = s->dlmod;
     S.lmodel_nd = s->dlmod_nd;
+    S.nodes = s->dnodes;
+    S.tris = s->dtris;
+    S.hits = s->dhits;
+    S.n_tris = d->n_triangles;
+    S.has_mesh = d->n_triangles > 0 ? 1 : 0;
+    {
+        // SDMM_MESH_BRUTE=1: the Li kernels loop over every triangle instead of walking the BVH (A/B)
+        const char* ev = std::getenv("SDMM_MESH_BRUTE");
+        S.mesh_brute = (ev && ev[0] == '1' && ev[1] == 0) ? 1 : 0;
+    }
     if (d->bsdf_params)
         for (int b = 0; b < d->n_bsdfs; ++b) {
             if (d->bsdf_params[kBsdfParams * b] == (float)kBsdfPhong) S.has_phong = 1;
@@ -575,6 +658,9 @@ void sdmm_scene_destroy(sdmm_scene* s) {
     if (s->dlmod) (void)hipFree(s->dlmod);
     if (s->dlmod_nd) (void)hipFree(s->dlmod_nd);
     if (s->drad) (void)hipFree(s->drad);
+    if (s->dnodes) (void)hipFree(s->dnodes);
+    if (s->dtris) (void)hipFree(s->dtris);
+    if (s->dhits) (void)hipFree(s->dhits);
     if (s->buf) (void)hipFree(s->buf);
     if (s->lt) (void)hipFree(s->lt);
     if (s->hcount) (void)hipHostFree(s->hcount);
@@ -591,6 +677,72 @@ int sdmm_scene_normalization(const sdmm_scene* s, float scene_min[3], float* spa
         if (tree_max) tree_max[a] = s->tmax[a];
     }
     if (spatial_norm) *spatial_norm = s->snorm;
+    return SDMM_OK;
+}
+
+int sdmm_scene_intersect(const sdmm_scene* s, int64_t nq, const float* const o[3], const float* const d[3], float mint,
+                         float maxt, int mode, int32_t* prim, float* t, void* hip_stream) {
+    if (!s || nq < 0 || (mode != 0 && mode != 1))
+        return fail(SDMM_E_INVALID, "sdmm_scene_intersect: invalid argument (mode 0 or 1)");
+    if (nq == 0) return SDMM_OK;
+    if (!o || !o[0] || !o[1] || !o[2] || !d || !d[0] || !d[1] || !d[2] || !prim || !t)
+        return fail(SDMM_E_INVALID, "sdmm_scene_intersect: NULL plane");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(launch_scene_intersect(s->S, nq, o, d, mint, maxt, mode, prim, t, (hipStream_t)hip_stream));
+    return SDMM_OK;
+}
+
+int sdmm_scene_intersect_host(const sdmm_scene_desc* desc, int64_t nq, const float* o, const float* d, float mint,
+                              float maxt, int mode, int32_t* prim, float* t) {
+    if (!desc || nq < 0 || (mode != 0 && mode != 1) || (nq > 0 && (!o || !d || !prim || !t)))
+        return fail(SDMM_E_INVALID, "sdmm_scene_intersect_host: invalid argument (mode 0 or 1)");
+    std::vector<QuadDev> qs;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    int rc = prep_quads(desc, "sdmm_scene_intersect_host", &qs, mn, mx);
+    if (rc) return rc;
+    MeshBvh mesh;
+    if (desc->n_triangles > 0) {
+        rc = prep_mesh(desc, "sdmm_scene_intersect_host", 0, &mesh);
+        if (rc) return rc;
+    }
+    // the device's float environment: denormals flushed (-fgpu-flush-denormals-to-zero)
+    const unsigned csr = _mm_getcsr();
+    _mm_setcsr(csr | 0x8040u);
+    const int nquads = (int)qs.size();
+    for (int64_t i = 0; i < nq; ++i) {
+        float tb;
+        int best = quads_closest(qs.data(), nquads, o + 3 * i, d + 3 * i, mint, maxt, tb);
+        if (desc->n_triangles > 0) mesh_closest_host(mesh, nquads, mode, o + 3 * i, d + 3 * i, mint, maxt, best, tb);
+        prim[i] = best;
+        t[i] = tb;
+    }
+    _mm_setcsr(csr);
+    return SDMM_OK;
+}
+
+int sdmm_mesh_bvh_dump(const sdmm_scene_desc* desc, int max_levels, int* n_nodes, int* levels, int cap_nodes,
+                       float* boxes, int32_t* children, int32_t* order) {
+    if (!desc || desc->n_triangles < 1 || max_levels < 0 || !n_nodes)
+        return fail(SDMM_E_INVALID, "sdmm_mesh_bvh_dump: invalid argument (a description with triangles)");
+    MeshBvh mesh;
+    const int rc = prep_mesh(desc, "sdmm_mesh_bvh_dump", max_levels, &mesh);
+    if (rc) return rc;
+    *n_nodes = (int)mesh.nodes.size();
+    if (levels) *levels = mesh.levels;
+    if (cap_nodes <= 0) return SDMM_OK;
+    if (cap_nodes < *n_nodes || !boxes || !children || !order)
+        return fail(SDMM_E_INVALID, "sdmm_mesh_bvh_dump: arrays for fewer nodes than the tree has");
+    for (size_t i = 0; i < mesh.nodes.size(); ++i) {
+        const BvhNode& N = mesh.nodes[i];
+        for (int c = 0; c < 2; ++c) {
+            for (int a = 0; a < 3; ++a) {
+                boxes[12 * i + 6 * c + a] = N.lo[c][a];
+                boxes[12 * i + 6 * c + 3 + a] = N.hi[c][a];
+            }
+            children[2 * i + c] = N.child[c];
+        }
+    }
+    for (size_t i = 0; i < mesh.tris.size(); ++i) order[i] = mesh.tris[i].id;
     return SDMM_OK;
 }
 

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mesh_bvh.h"
+
 namespace sdmm {
 
 // ---- counter-based RNG (host + device; oracle/sdmm_oracle_train.c restates) ----
@@ -66,7 +68,39 @@ struct SceneDev {
     float smin[3], snorm;
     int has_phong;        // some BSDF is Phong: the Li kernels' PHONG variants run
     int has_dielectric;   // some BSDF is a rough dielectric: their DIEL variants run
+    // triangle mesh (mesh_bvh.h; primitive ids n_quads + i): null / 0 without one
+    const BvhNode* nodes;
+    const MeshTri* tris;      // leaf order
+    const MeshHit* hits;      // by triangle index
+    int n_tris;
+    int has_mesh;         // the Li kernels' MESH variants run
+    int mesh_brute;       // SDMM_MESH_BRUTE=1: the loop over all triangles instead of the BVH (A/B)
 };
+
+// closest quad with t in (mint, maxt), the lowest id on equal t (strict <);
+// -1: none, *t_hit = maxt then.  Host + device, bitwise alike.
+__host__ __device__ __forceinline__ int quads_closest(const QuadDev* quads, int n_quads, const float o[3],
+                                                      const float d[3], float mint, float maxt, float& t_hit) {
+#pragma clang fp contract(off)
+    int best = -1;
+    float tb = maxt;
+    for (int q = 0; q < n_quads; ++q) {
+        const QuadDev& Q = quads[q];
+        const float denom = d[0] * Q.n[0] + d[1] * Q.n[1] + d[2] * Q.n[2];
+        if (denom == 0.0f) continue;
+        const float r0[3] = {Q.p0[0] - o[0], Q.p0[1] - o[1], Q.p0[2] - o[2]};
+        const float t = (r0[0] * Q.n[0] + r0[1] * Q.n[1] + r0[2] * Q.n[2]) / denom;
+        if (!(t > mint && t < tb)) continue;
+        const float r[3] = {o[0] + t * d[0] - Q.p0[0], o[1] + t * d[1] - Q.p0[1], o[2] + t * d[2] - Q.p0[2]};
+        const float a = r[0] * Q.g1[0] + r[1] * Q.g1[1] + r[2] * Q.g1[2];
+        const float b = r[0] * Q.g2[0] + r[1] * Q.g2[1] + r[2] * Q.g2[2];
+        if (a < 0.0f || a > 1.0f || b < 0.0f || b > 1.0f) continue;
+        tb = t;
+        best = q;
+    }
+    t_hit = tb;
+    return best;
+}
 
 struct PathsDev {
     float *px, *py, *pz;     // current hit point
@@ -74,7 +108,7 @@ struct PathsDev {
     float *tr, *tg, *tb;     // throughput
     float *lr, *lg, *lb;     // Li
     int* depth;              // rRec.depth; -1 once the path has ended
-    int* quad;               // hit quad
+    int* quad;               // hit primitive (a quad, or n_quads + triangle)
     int* nv;                 // saved vertices
     int* nray;               // traced bounce rays (a delta bounce saves no vertex)
     float* rec;              // vertex records: rec[(f * V + v) * P + p]

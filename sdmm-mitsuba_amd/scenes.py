@@ -235,7 +235,8 @@ def load_learned_nd(path=LEARNED_PHONG):
 def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, learned=LEARNED_CONDUCTOR, phong=(),
                 phong_learned=LEARNED_PHONG, phong_specular=(0.4, 0.4, 0.4), phong_exponent=30.0, dielectric=(),
                 dielectric_learned=LEARNED_DIELECTRIC, dielectric_alpha=0.1, dielectric_ior=(1.5046, 1.000277),
-                dielectric_specular=(1.0, 1.0, 1.0), dielectric_transmittance=(1.0, 1.0, 1.0), dielectric_lift=0.0):
+                dielectric_specular=(1.0, 1.0, 1.0), dielectric_transmittance=(1.0, 1.0, 1.0), dielectric_lift=0.0,
+                mesh=()):
     """sdmm_scene_desc fields for the Cornell Box (numpy arrays).  plastic:
     names of BSDFs (e.g. "TallBox", "ShortBox", "Floor") rendered as smooth
     plastic over their diffuse reflectance (a delta specular lobe beside a
@@ -255,9 +256,14 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
     `dielectric_learned` (None: no model) -- the stand-in of
     tools/make_learned_dielectric.py by default.  dielectric_lift raises a
     dielectric cube by that much along y: the cubes stand on the floor, and a
-    glass box's bottom face would be coplanar with it."""
+    glass box's bottom face would be coplanar with it.  mesh: names of the
+    cubes ("ShortBox", "TallBox") given as triangles (quads_to_triangles of
+    their faces, the description's mesh fields) instead of quads."""
     names = list(_BSDFS)
     quads, bsdf, flip, emitter = [], [], [], []
+    mesh_quads, mesh_bsdf = [], []
+    if set(mesh) - {name for _, name in _CUBES}:
+        raise ValueError(f"mesh: only the cubes {[name for _, name in _CUBES]} can be triangles")
     for m, name, fl in _RECTS:
         quads.append(np.concatenate(_rect(_mat(m))))
         bsdf.append(names.index(name)); flip.append(int(fl)); emitter.append(-1)
@@ -266,12 +272,19 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
         if name in dielectric:
             M[1, 3] += dielectric_lift
         for f in _cube_faces(M):
+            if name in mesh:
+                mesh_quads.append(np.concatenate(f))
+                mesh_bsdf += [names.index(name)] * 2
+                continue
             quads.append(np.concatenate(f))
             bsdf.append(names.index(name)); flip.append(0); emitter.append(-1)
     quads.append(np.concatenate(_rect(_mat(_LIGHT))))
     bsdf.append(names.index("Light")); flip.append(0); emitter.append(0)
     cam = np.array([float(x) for x in _CAMERA.split()], np.float32)
     extra = {}
+    if mesh_quads:
+        v, t = quads_to_triangles(np.asarray(mesh_quads, np.float32))
+        extra.update(mesh_vertices=v.reshape(-1), triangles=t.reshape(-1), tri_bsdf=np.asarray(mesh_bsdf, np.int32))
     refl = {n: _BSDFS[n] for n in names}
     if plastic or conductor or phong or dielectric:
         kinds = [set(plastic), set(conductor), set(phong), set(dielectric)]
@@ -310,6 +323,135 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
         "radiance": spectrum_to_rgb(_LIGHT_SPD).astype(np.float32),
         "camera_to_world": cam,
         "fov_x_deg": 35.0,
+        "near_clip": 1e-2,
+        "width": width,
+        "height": height,
+    }
+
+
+def torus_mesh(nu, nv, R=1.0, r=0.4, to_world=None):
+    """A torus about the y axis (centre circle of radius R in the xz plane,
+    tube radius r) as nu x nv quads of two triangles: (vertices [nu * nv, 3]
+    float32, triangles [2 * nu * nv, 3] int32), counter-clockwise seen from
+    outside.  to_world: a 3x4 or 4x4 matrix applied to the vertices."""
+    u = 2.0 * np.pi * np.arange(nu) / nu
+    v = 2.0 * np.pi * np.arange(nv) / nv
+    uu, vv = np.meshgrid(u, v, indexing="ij")
+    ring = R + r * np.cos(vv)
+    P = np.stack([ring * np.cos(uu), r * np.sin(vv), ring * np.sin(uu)], -1).reshape(-1, 3)
+    if to_world is not None:
+        M = np.asarray(to_world, np.float64).reshape(-1, 4)[:3]
+        P = P @ M[:, :3].T + M[:, 3]
+    i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+    a = (i * nv + j).reshape(-1)
+    b = (((i + 1) % nu) * nv + j).reshape(-1)
+    c = (((i + 1) % nu) * nv + (j + 1) % nv).reshape(-1)
+    d = (i * nv + (j + 1) % nv).reshape(-1)
+    # outward: (dP/dv) x (dP/du) for this parametrisation
+    tris = np.concatenate([np.stack([a, d, c], -1), np.stack([a, c, b], -1)], 1).reshape(-1, 3)
+    if to_world is not None and np.linalg.det(M[:, :3]) < 0:
+        tris = tris[:, ::-1]
+    return P.astype(np.float32), np.ascontiguousarray(tris, np.int32)
+
+
+def convex_mesh():
+    """An octahedron subdivided once and pushed to the unit sphere: (vertices
+    [18, 3] float32, triangles [32, 3] int32), counter-clockwise seen from
+    outside.  Convex, so no ray leaving it meets it again."""
+    V = [(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1)]
+    F = [(0, 2, 4), (2, 1, 4), (1, 3, 4), (3, 0, 4), (2, 0, 5), (1, 2, 5), (3, 1, 5), (0, 3, 5)]
+    verts = [np.asarray(v, np.float64) for v in V]
+    mid = {}
+
+    def midpoint(i, j):
+        key = (min(i, j), max(i, j))
+        if key not in mid:
+            m = verts[i] + verts[j]
+            verts.append(m / np.linalg.norm(m))
+            mid[key] = len(verts) - 1
+        return mid[key]
+    tris = []
+    for a, b, c in F:
+        ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+        tris += [(a, ab, ca), (ab, b, bc), (ca, bc, c), (ab, bc, ca)]
+    return np.asarray(verts, np.float32), np.asarray(tris, np.int32)
+
+
+def quads_to_triangles(quads):
+    """Each quad (p0, e1, e2; [n, 9] or flat) as the triangles (p0, p0 + e1,
+    p0 + e1 + e2) and (p0, p0 + e1 + e2, p0 + e2) -- the quad's winding:
+    (vertices [4 n, 3] float32, triangles [2 n, 3] int32)."""
+    q = np.asarray(quads, np.float32).reshape(-1, 3, 3)
+    p0, e1, e2 = q[:, 0], q[:, 1], q[:, 2]
+    verts = np.stack([p0, p0 + e1, p0 + e1 + e2, p0 + e2], 1).reshape(-1, 3)
+    base = 4 * np.arange(len(q), dtype=np.int32)[:, None]
+    tris = np.concatenate([base + np.array([0, 1, 2], np.int32), base + np.array([0, 2, 3], np.int32)], 1)
+    return verts.astype(np.float32), np.ascontiguousarray(tris.reshape(-1, 3), np.int32)
+
+
+def _look_at(origin, target, up):
+    """Mitsuba's lookAt as a row-major 4x4 camera-to-world (camera looks along +z)."""
+    o, t, u = (np.asarray(x, np.float64) for x in (origin, target, up))
+    z = (t - o) / np.linalg.norm(t - o)
+    x = np.cross(u, z)
+    x /= np.linalg.norm(x)
+    y = np.cross(z, x)
+    M = np.eye(4)
+    M[:3, 0], M[:3, 1], M[:3, 2], M[:3, 3] = x, y, z, o
+    return M.reshape(-1).astype(np.float32)
+
+
+def torus_scene(width=640, height=360, nu=96, nv=48, glass=True):
+    """The Torus configuration's stand-in (test-suite/scenes/torus/torus.xml):
+    a diffuse torus (reflectance .8, .8, .4; torus_mesh(nu, nv), R 1, r 0.4,
+    lying on the floor) under a rough-dielectric case of quads (alpha 0.05,
+    ior 1.5, the shipped dielectric_4c learned model) on a diffuse floor.  The
+    reference lights the scene with `sunsky`; the device Li has no environment
+    emitter, so a closed room of quads with a ceiling lamp is the stated
+    proxy.  The camera follows torus.xml's framing loosely: above and in front
+    of the case, looking down at the torus."""
+    names = ["Room", "Floor", "Torus", "Glass", "Light"]
+    refl = {"Room": (0.6, 0.6, 0.6), "Floor": (0.5, 0.5, 0.5), "Torus": (0.8, 0.8, 0.4), "Glass": (1.0, 1.0, 1.0),
+            "Light": (0.0, 0.0, 0.0)}
+    quads, bsdf, emitter = [], [], []
+
+    def box(lo, hi, name, inward, skip_bottom=False):
+        lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+        M = np.zeros((3, 4))
+        M[:, :3] = np.diag(0.5 * (hi - lo))
+        M[:, 3] = 0.5 * (hi + lo)
+        for k, (p0, e1, e2) in enumerate(_cube_faces(M)):
+            if skip_bottom and k == 3:      # the face y = lo (ax 1, s -1)
+                continue
+            quads.append(np.concatenate((p0, e2, e1) if inward else (p0, e1, e2)))
+            bsdf.append(names.index(name)); emitter.append(-1)
+    box((-4.0, 0.0, -4.0), (4.0, 5.0, 4.0), "Room", inward=True, skip_bottom=True)
+    quads.append(np.array([-4.0, 0.0, -4.0, 0.0, 0.0, 8.0, 8.0, 0.0, 0.0]))      # floor, normal +y
+    bsdf.append(names.index("Floor")); emitter.append(-1)
+    quads.append(np.array([-1.5, 4.99, -1.5, 3.0, 0.0, 0.0, 0.0, 0.0, 3.0]))     # lamp, normal -y
+    bsdf.append(names.index("Light")); emitter.append(0)
+    bp = np.zeros((len(names), 8), np.float32)
+    extra = {}
+    if glass:
+        # the case stands 0.02 above the floor: its bottom face is not coplanar with it
+        box((-1.7, 0.02, -1.7), (1.7, 1.2, 1.7), "Glass", inward=False)
+        bp[names.index("Glass")], refl["Glass"] = dielectric_params(int_ior=1.5, ext_ior=1.0, alpha=0.05)
+        model = load_learned_nd(LEARNED_DIELECTRIC)
+        extra["learned_models_nd"] = [model if nm == "Glass" else None for nm in names]
+    T = np.array([[1.0, 0, 0, 0], [0, 1.0, 0, 0.45], [0, 0, 1.0, 0]])
+    verts, tris = torus_mesh(nu, nv, 1.0, 0.4, to_world=T)
+    return {**extra,
+        "quads": np.asarray(quads, np.float32).reshape(-1),
+        "bsdf": np.asarray(bsdf, np.int32),
+        "bsdf_params": bp.reshape(-1),
+        "reflectance": np.asarray([refl[n] for n in names], np.float32).reshape(-1),
+        "emitter": np.asarray(emitter, np.int32),
+        "radiance": np.asarray([12.0, 12.0, 12.0], np.float32),
+        "mesh_vertices": verts.reshape(-1),
+        "triangles": tris.reshape(-1),
+        "tri_bsdf": np.full(len(tris), names.index("Torus"), np.int32),
+        "camera_to_world": _look_at((0.0, 3.2, 3.6), (0.0, 0.4, 0.0), (0.0, 1.0, 0.0)),
+        "fov_x_deg": 45.0,
         "near_clip": 1e-2,
         "width": width,
         "height": height,

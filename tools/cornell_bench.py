@@ -6,6 +6,15 @@
 --phong NAME ...   those BSDFs as Phong with the learned SDMM5 instead
 --dielectric NAME ...  those BSDFs as rough dielectrics (glass) with the
                    learned SDMM5, a cube lifted off the floor by 0.02
+--torus            the torus scene instead (scenes.torus_scene: a triangle mesh
+                   under a glass case; --tess NUxNV its tessellation, default
+                   96x48) through the same loop; SDMM_MESH_BRUTE=1 in the
+                   environment makes the Li kernels loop over all triangles
+                   instead of walking the BVH (A/B)
+--intersect N      with --torus: also time sdmm_scene_intersect on 2^N
+                   camera-like rays against the scene without its case, BVH
+                   and brute force (rays/s), and a plain unguided 8-spp pass;
+                   --repeat 0 then skips the training loop
 --repeat N         N timed lines per configuration (A/B runs: medians, spreads)
 """
 import functools
@@ -31,6 +40,9 @@ if __name__ == "__main__":
     ap.add_argument("--glossy", nargs="*", default=[], help="BSDFs rendered as rough conductors")
     ap.add_argument("--phong", nargs="*", default=[], help="BSDFs rendered as Phong (learned SDMM5)")
     ap.add_argument("--dielectric", nargs="*", default=[], help="BSDFs rendered as rough dielectrics (learned SDMM5)")
+    ap.add_argument("--torus", action="store_true", help="the torus scene (triangle mesh) instead of the Cornell box")
+    ap.add_argument("--tess", default="96x48", help="--torus: tessellation NUxNV")
+    ap.add_argument("--intersect", type=int, default=0, help="--torus: time Scene.intersect on 2^N rays")
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--summary", action="store_true", help="one line per run, no per-iteration lines")
     a = ap.parse_args()
@@ -43,11 +55,71 @@ if __name__ == "__main__":
         scenes = importlib.import_module("sdmm_mitsuba_amd.scenes")
         scenes.cornell_box = functools.partial(scenes.cornell_box, dielectric=tuple(a.dielectric),
                                                dielectric_lift=0.02)
+    if a.torus:
+        import os
+        import time
+        scenes = importlib.import_module("sdmm_mitsuba_amd.scenes")
+        nu, nv = (int(x) for x in a.tess.lower().split("x"))
+        scenes.cornell_box = lambda w, h, **kw: scenes.torus_scene(w, h, nu, nv)
+        brute = os.environ.get("SDMM_MESH_BRUTE") == "1"
+        if a.intersect:
+            dev = torch.device("cuda", 0)
+            # (without the glass case: every ray would stop at it, and the walk would have nothing to do)
+            sc = pkg.Scene(scenes.torus_scene(640, 360, nu, nv, glass=False))
+            n = 1 << a.intersect
+            g = torch.Generator(device=dev).manual_seed(1)
+            # camera-like: one origin, directions in a cone about the view axis
+            cam = torch.tensor([0.0, 3.2, 3.6], device=dev)
+            axis = torch.tensor([0.0, -2.8, -3.6], device=dev)
+            dirs = axis / axis.norm() + 0.5 * (torch.rand(n, 3, device=dev, generator=g) - 0.5)
+            dirs = dirs / dirs.norm(dim=1, keepdim=True)
+            o = [cam[i].expand(n).contiguous() for i in range(3)]
+            d = [dirs[:, i].contiguous() for i in range(3)]
+            # device time by events over several back-to-back launches (the
+            # call also allocates its two output planes from torch's cache),
+            # three such groups, the best one reported
+            for mode in (0, 1):
+                launches = 3 if mode else 20
+                sc.intersect(o, d, 1e-2, float("inf"), mode)
+                torch.cuda.synchronize()
+                times = []
+                for _ in range(3):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(launches):
+                        prim, _ = sc.intersect(o, d, 1e-2, float("inf"), mode)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times.append(e0.elapsed_time(e1) / launches)
+                print(json.dumps({"intersect": "brute" if mode else "bvh", "triangles": 2 * nu * nv, "rays": n,
+                                  "launches_per_group": launches, "ms": [round(t, 4) for t in times],
+                                  "rays_per_s": n / (min(times) * 1e-3),
+                                  "mesh_hits": int((prim >= sc.n_quads).sum())}), flush=True)
+            # a plain unguided pass (8 spp, no training) of the scene with its case
+            sc = pkg.Scene(scenes.torus_scene(640, 360, nu, nv))
+            _, _, tmin, tmax = sc.normalization()
+            tree = pkg.STree(tmin, tmax)
+            tree.split_to_depth(2)
+            times = []
+            for i in range(4):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                sc.render(tree, None, spp=8, guided=False, seed=1 + i)
+                torch.cuda.synchronize()
+                times.append(time.perf_counter() - t0)
+            print(json.dumps({"unguided_pass_ms": [round(t * 1e3, 3) for t in times[1:]], "triangles": 2 * nu * nv,
+                              "mesh": "brute" if brute else "bvh"}), flush=True)
     for K in a.K:
       for mode in a.modes:
         for _ in range(a.repeat):
             out = bench.cornell_bench(pkg, torch.device("cuda", 0), None, 1, optimize_async=mode, K=K,
                                       product=a.product, glossy=tuple(a.glossy))
+            if a.torus:
+                out["workload"] = out["workload"].replace("Cornell Box", f"Torus scene ({a.tess}, " +
+                                                          ("brute force" if brute else "BVH") + ")")
+                its = out["iterations"]
+                out["first_pass_ms"] = round(its[0]["ms"], 3)     # unguided render + push + optimize
+                out["guided_pass_ms"] = [round(x["ms"], 3) for x in its if not x["train"]]
             if a.phong:
                 out["workload"] += " (Phong " + "/".join(a.phong) + ")"
             if a.dielectric:

@@ -574,23 +574,95 @@ def bsdf_phong(params, rho, wi, u=None, wo=None):
     return out, value, float(pdf[0])
 
 
+def bsdf_roughdielectric(params, trans, wi, u=None, wo=None):
+    """or_bsdf_roughdielectric, local frame, in the shape of
+    sdmm_bsdf_roughdielectric_host: RoughDielectric::sample (u (3) given: (wo,
+    weight, pdf, bRec.eta)) or eval and pdf at a given wo ((wo, eval, pdf, the
+    relative index that direction crosses))."""
+    params = np.ascontiguousarray(params, np.float32)
+    trans = np.ascontiguousarray(trans, np.float32)
+    wi = np.ascontiguousarray(wi, np.float32)
+    assert (u is None) != (wo is None)
+    out = np.zeros(3, np.float32) if wo is None else np.array(wo, np.float32)
+    value = np.zeros(3, np.float32)
+    pe = np.zeros(2, np.float32)
+    f = lib().or_bsdf_roughdielectric
+    f.restype = None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    eta = C.c_void_p(pe.ctypes.data + 4)
+    if u is not None:
+        uu = np.ascontiguousarray(u, np.float32)
+        f(vp(params), vp(trans), vp(wi), vp(uu), None, vp(out), vp(value), vp(pe), None, None, eta)
+    else:
+        f(vp(params), vp(trans), vp(wi), None, vp(out), None, None, None, vp(value), vp(pe), eta)
+    return out, value, float(pe[0]), float(pe[1])
+
+
+def _mesh_args(desc):
+    """The mesh fields of a description (the keys pkg.Scene reads) as arrays
+    kept alive by the caller: (vertices, n_vertices, triangles, n_triangles,
+    tri_bsdf, tri_emitter, tri_flip_normals); absent ones None / 0."""
+    i32 = lambda k: np.ascontiguousarray(desc[k], np.int32) if desc.get(k) is not None else None
+    tris = i32("triangles")
+    nt = 0 if tris is None else tris.size // 3
+    verts = np.ascontiguousarray(desc["mesh_vertices"], np.float32) if nt else None
+    if nt == 0:
+        return None, 0, None, 0, None, None, None
+    return verts, verts.size // 3, tris, nt, i32("tri_bsdf"), i32("tri_emitter"), i32("tri_flip_normals")
+
+
+def _quad_args(desc):
+    """(quads, flip_normals, bsdf, emitter, n_quads) of a description; a mesh-only one has none."""
+    if "quads" not in desc or np.asarray(desc["quads"]).size == 0:
+        return None, None, None, None, 0
+    quads = np.ascontiguousarray(desc["quads"], np.float32)
+    i32 = lambda k: np.ascontiguousarray(desc[k], np.int32) if desc.get(k) is not None else None
+    return quads, i32("flip_normals"), i32("bsdf"), i32("emitter"), quads.size // 9
+
+
+def li_intersect(desc, o, d, mint=1e-4, maxt=float("inf")):
+    """or_li_intersect: the oracle's closest hit of rays o, d ([n, 3]) against
+    a description's quads and triangles (a loop over all of them) ->
+    (prim int32[n], -1: none; t float32[n], maxt without a hit)."""
+    quads, flip, _, _, nq = _quad_args(desc)
+    verts, nverts, tris, nt, _, _, _ = _mesh_args(desc)
+    o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    assert o.shape == d.shape
+    prim = np.empty(len(o), np.int32)
+    t = np.empty(len(o), np.float32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    f = lib().or_li_intersect
+    f.restype = C.c_int
+    rc = f(vp(quads), vp(flip), C.c_int(nq), vp(verts), C.c_int(nverts), vp(tris), C.c_int(nt), C.c_int64(len(o)),
+           vp(o), vp(d), C.c_float(mint), C.c_float(maxt), vp(prim), vp(t))
+    assert rc == 0, "or_li_intersect failed"
+    return prim, t
+
+
 def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_depth=10, rr_depth=10, h=0.5,
-              V=9, seed=0, pixels=None, learned=None, threads=1):
+              V=9, seed=0, pixels=None, learned=None, threads=1, rr_eta_one=False):
     """SDMMRenderer::Li restated on the CPU (sdmm_oracle_li.inc) for a
     scene description (scenes.cornell_box() fields), the tree (aabb (n, 6),
     child (n, 2)) and per-node oracle Mixtures (None: no trained context).
     learned: (weights (B, M), means (B, M, 3), covs (B, M, 4), diffuse (B,))
     for sampleProduct.  desc["learned_models"] / desc["learned_models_nd"]:
-    the conductors' SDMM4s / the Phong BSDFs' SDMM5s.  Returns dict image
-    (3, H, W), image_sqr, rec (16, V, P), nv (P,), comps (bounces, P),
-    hit_bsdf (bounces, P): the BSDF each live bounce scattered at (-1: none)."""
+    the conductors' SDMM4s / the Phong BSDFs' and rough dielectrics' SDMM5s;
+    desc["mesh_vertices"] / ["triangles"] / ["tri_bsdf"] / ["tri_emitter"] /
+    ["tri_flip_normals"]: the triangle mesh (a description may have no quads).
+    rr_eta_one: a switch for the tests alone -- roulette with the path's
+    relative index taken as 1.  Returns dict image (3, H, W), image_sqr, rec
+    (16, V, P), nv (P,), comps (bounces, P), hit_bsdf (bounces, P): the BSDF
+    each live bounce scattered at (-1: none), inside (bounces, P): 1 where
+    that bounce met the surface from behind, 0 from the front, -1 none."""
     W, H = int(desc["width"]), int(desc["height"])
     lo, hi = (0, W * H) if pixels is None else pixels
     P = (hi - lo) * spp
     f32 = lambda a: np.ascontiguousarray(a, np.float32)
     i32 = lambda a: np.ascontiguousarray(a, np.int32)
-    quads, flip, bsdf = f32(desc["quads"]), i32(desc["flip_normals"]), i32(desc["bsdf"])
-    refl, em, rad = f32(desc["reflectance"]), i32(desc["emitter"]), f32(desc["radiance"])
+    quads, flip, bsdf, em, nq = _quad_args(desc)
+    mesh = _mesh_args(desc)
+    refl, rad = f32(desc["reflectance"]), f32(desc["radiance"])
     cam = f32(desc["camera_to_world"])
     mn = np.ascontiguousarray(np.asarray(aabb)[:, :3].reshape(-1), np.float32)
     mx = np.ascontiguousarray(np.asarray(aabb)[:, 3:].reshape(-1), np.float32)
@@ -610,6 +682,7 @@ def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_d
     bounces = max_depth - 1 if max_depth > 0 else V
     comps = np.full((bounces, P), -9, np.int32)
     hit_bsdf = np.full((bounces, P), -1, np.int32)
+    inside = np.full((bounces, P), -1, np.int32)
     if learned is not None:
         bw, bm, bc, bd = f32(learned[0]), f32(learned[1]), f32(learned[2]), np.ascontiguousarray(learned[3], np.uint8)
         M = bw.shape[1]
@@ -619,17 +692,19 @@ def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_d
         M = 0
     f = lib().or_li_render
     f.restype = C.c_int
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
     bpar = f32(desc["bsdf_params"]) if "bsdf_params" in desc else None
     lmod = pack_learned_models(desc.get("learned_models"), len(refl) // 3)
     lmod_nd = pack_learned_models_nd(desc.get("learned_models_nd"), len(refl) // 3)
-    rc = f(vp(quads), vp(flip), vp(bsdf), C.c_int(len(bsdf)), vp(refl), vp(bpar) if bpar is not None else None,
+    rc = f(vp(quads), vp(flip), vp(bsdf), C.c_int(nq), vp(refl), vp(bpar),
            vp(em), vp(rad), vp(cam),
            C.c_float(desc["fov_x_deg"]), C.c_float(desc["near_clip"]), C.c_int(W), C.c_int(H), vp(mn), vp(mx),
            vp(ch), tab, C.c_int(int(guided)), C.c_int(spp), C.c_int(max_depth), C.c_int(rr_depth), C.c_float(h),
            C.c_int(V), C.c_uint64(seed), C.c_int64(lo), C.c_int64(hi), C.c_int(1 if learned is not None else 0),
            vp(bw), vp(bm), vp(bc), vp(bd), C.c_int(M), C.c_int(kmax), vp(image), vp(image_sqr), vp(rec), vp(nv),
            vp(comps), C.c_int(threads), vp(lmod) if lmod is not None else None,
-           vp(lmod_nd) if lmod_nd is not None else None, vp(hit_bsdf))
+           vp(lmod_nd) if lmod_nd is not None else None, vp(hit_bsdf), vp(mesh[0]), C.c_int(mesh[1]), vp(mesh[2]),
+           C.c_int(mesh[3]), vp(mesh[4]), vp(mesh[5]), vp(mesh[6]), vp(inside), C.c_int(int(rr_eta_one)))
     assert rc == 0, "or_li_render failed"
-    return {"image": image, "image_sqr": image_sqr, "rec": rec, "nv": nv, "comps": comps, "hit_bsdf": hit_bsdf}
+    return {"image": image, "image_sqr": image_sqr, "rec": rec, "nv": nv, "comps": comps, "hit_bsdf": hit_bsdf,
+            "inside": inside}

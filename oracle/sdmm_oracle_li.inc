@@ -1,9 +1,11 @@
 /* sdmm_oracle_li.inc -- CPU ORACLE (test infrastructure only; included by
  * sdmm_oracle.c).  SDMMRenderer::Li (mitsuba/src/integrators/sdmm/
  * sdmm_proc.cpp:592-871) over an analytic scene of parallelograms (Mitsuba
- * rectangles; a cube is six) with diffuse BSDFs and one-sided area emitters --
- * the scenes the library's device Li renders (sdmm_li_render) -- one path at
- * a time, restated from the reference as text:
+ * rectangles; a cube is six) and an optional triangle mesh, with diffuse,
+ * plastic, rough-conductor, Phong and rough-dielectric BSDFs and one-sided
+ * area emitters -- the scenes the library's device Li renders
+ * (sdmm_li_render) -- one path at a time, restated from the reference as
+ * text:
  *
  *   :641-677   first intersection, emission seen directly (before any vertex)
  *   :649-691   rRec.depth 1 .. maxDepth-1 scatter; the depth cap (:684-685)
@@ -45,14 +47,46 @@
  *              conditioned on (theta_i, max specular channel, log max(1,
  *              exponent)), pruned to 2 with component 1 (the diffuse one)
  *              forced -- li_learned_nd_conditional -- then rotate_to_wo
+ *   a rough dielectric (bsdf kind 4; bsdfs/roughdielectric.cpp eval :317-395,
+ *              pdf :397-469, sample :560-662 over microfacet.h; libcore/
+ *              util.cpp fresnelDielectricExt :651-681, refract :767-772):
+ *              li_roughdielectric_* in double between float inputs and outputs
+ *              (the library's documented contract).  The restatement keeps
+ *              the library's operation order, and with it the shape of
+ *              csrc/bsdf_roughdielectric.h (also what a void sample leaves in
+ *              wo), because every rounding of the double arithmetic has to
+ *              agree for the Li comparison to be bitwise: "equals the host
+ *              call bit for bit" therefore shows only that the two texts say
+ *              the same, not that either is right.  The independent evidence
+ *              is the float64 numpy restatement and the furnace albedo
+ *              (tests/test_li_oracle_dielectric.py).  The one two-sided
+ *              material: alive from either side, dead at wi . n == 0 or with
+ *              reflectance and transmittance both zero; sampled in Frame(n) of
+ *              the stored normal whatever the side, the lobe's uniform
+ *              (sampler->next1D(), :601) dimension 7 of the bounce's stream;
+ *              the guide's direction evaluated over the whole sphere, bRec.eta
+ *              there what sample would have set (li_roughdielectric_crossed);
+ *              a vertex saved inside the medium carries -n (sdmm_proc.cpp
+ *              :765-767); in a product bounce getDMM (:198-211): none from
+ *              inside (:199), else its SDMM5 at (theta_i, alpha, eta), pruned
+ *              to 2, no forced component
+ *   :604, :788 the path's relative index: eta = 1, times bRec.eta of every
+ *              bounce; :864 the roulette's q = min(max(thr) eta^2, 0.95)
+ *
+ * Triangles: Triangle::rayIntersect (include/mitsuba/core/triangle.h:109-145)
+ * in float -- li_tri_intersect -- over every triangle in a loop, no hierarchy;
+ * the closest hit of li_intersect has t in (mint, maxt), the smallest t, on
+ * exactly equal t the lowest primitive id, quads before triangles (primitive
+ * n_quads + i is triangle i); face normals normalize((p1 - p0) x (p2 - p0)),
+ * flipped on request; the scene box reaches over the mesh vertices.
  *
  * The product's lobes per table row, lM: the device gives every compact query
- * a row of its own with max(M, 2) lobes as soon as some quad of the scene has
- * a rough-conductor or a Phong BSDF -- whether or not that BSDF carries a
- * learned model (sdmm_scene_create sets per_query_lobes from the BSDF kinds
- * alone; extend_learned re-strides the caller's rows, the extra lobes weight
- * 0) -- and M lobes otherwise.  or_li_render follows that rule, so the
- * component indices k * lM + j agree.
+ * a row of its own with max(M, 2) lobes as soon as some quad or triangle of
+ * the scene has a rough-conductor, a Phong or a rough-dielectric BSDF --
+ * whether or not that BSDF carries a learned model (sdmm_scene_create sets
+ * per_query_lobes from the BSDF kinds alone; extend_learned re-strides the
+ * caller's rows, the extra lobes weight 0) -- and M lobes otherwise.
+ * or_li_render follows that rule, so the component indices k * lM + j agree.
  *
  * Scene conventions (Mitsuba): diffuse BSDFs sample the cosine hemisphere
  * (warp::squareToCosineHemisphere, concentric map) in Frame(n) (Mitsuba's
@@ -62,16 +96,18 @@
  * are the library's counter-based uniforms (or_rng_uniform,
  * sdmm_oracle_train.c): stream 0 the camera (dims 0-1 the pixel jitter),
  * stream 1 + b bounce b (dims 0-1 BSDF sample, 2 BSDF/guide choice, 3-5 the
- * guide sample, 6 roulette) -- not Mitsuba's sampler, which cannot be run
- * here.  Float arithmetic with -ffp-contract=off; sin/cos of the cosine map
- * as the correctly rounded (float)f((double)x).
+ * guide sample, 6 roulette, 7 the dielectric's lobe) -- not Mitsuba's sampler,
+ * which cannot be run here.  Float arithmetic with -ffp-contract=off; sin/cos
+ * of the cosine map as the correctly rounded (float)f((double)x).
  *
  * The guide on each leaf is this oracle's conditional (or_conditional_*) and
  * product (or_product_*) on that leaf's parameters.  node_mix[v] NULL: the
  * node has no trained context.  Output layout as sdmm_li_render: image /
  * image_sqr planes [3][W*H]; vertex field f of vertex v of path p at
  * rec[(f * V + v) * P + p]; comps[b * P + p]: the guided query's component
- * index (-1 no valid conditional, -2 the BSDF sample was chosen, -9 no query).
+ * index (-1 no valid conditional, -2 the BSDF sample was chosen, -9 no query);
+ * hit_bsdf[b * P + p]: the BSDF bounce b scattered at (-1: none); inside[b * P
+ * + p]: 1 where it met the surface from behind, 0 from the front, -1 none.
  */
 #include <pthread.h>
 
@@ -80,9 +116,18 @@ typedef struct {
     int bsdf, emitter;
 } li_quad;
 
+/* a triangle of the mesh: corner and edges (p1 - p0, p2 - p0), the unit face
+ * normal normalize((p1 - p0) x (p2 - p0)) with the flip applied */
+typedef struct {
+    float p0[3], e1[3], e2[3], n[3];
+    int bsdf, emitter;
+} li_tri;
+
 typedef struct {
     li_quad* quads;
     int nq;
+    li_tri* tris;   /* primitive id of triangle i: nq + i */
+    int nt;
     const float* refl;
     const float* bpar;   /* 8 per BSDF (include/sdmm_gpu.h bsdf_params); NULL: all diffuse */
     const float* lmodel; /* LI_L4_STRIDE per BSDF: [M, M SDMM4 records]; NULL: no learned models */
@@ -106,14 +151,18 @@ int or_stree_find(const float* mn, const float* mx, const int* child, const floa
 
 /* rectangle / cube faces as parallelograms: normal = (e1 x e2) / |e1 x e2|,
  * flipped on request; dual vectors g1 = (e2 x n) / (e1 . (e2 x n)), g2 =
- * (n x e1) / (e2 . (n x e1)) with the unnormalised n; the scene box over the
- * quads' corners (getAABBWithoutCamera), spatialNormalization = its largest
- * extent (volpath_sdmm.cpp:375-393) */
-static int li_scene_build(li_scene* S, const float* quads, const int32_t* flip, const int32_t* bsdf, int nq,
-                          const float* refl, const float* bpar, const int32_t* emitter, const float* rad,
-                          const float cam[16], float fov, float near_clip, int width, int height) {
-    S->quads = (li_quad*)malloc(sizeof(li_quad) * (size_t)nq);
+ * (n x e1) / (e2 . (n x e1)) with the unnormalised n.  The mesh (nt > 0):
+ * triangle i over the vertices tri[3 i .. 3 i + 2], its face normal as above.
+ * The scene box over the quads' corners and every mesh vertex
+ * (getAABBWithoutCamera), spatialNormalization = its largest extent
+ * (volpath_sdmm.cpp:375-393).  nq == 0 (a mesh alone) is a scene. */
+static int li_geometry_build(li_scene* S, const float* quads, const int32_t* flip, const int32_t* bsdf, int nq,
+                             const int32_t* emitter, const float* verts, int nverts, const int32_t* tri, int nt,
+                             const int32_t* tri_bsdf, const int32_t* tri_emitter, const int32_t* tri_flip) {
+    S->quads = (li_quad*)malloc(sizeof(li_quad) * (size_t)(nq > 0 ? nq : 1));
     S->nq = nq;
+    S->tris = (li_tri*)malloc(sizeof(li_tri) * (size_t)(nt > 0 ? nt : 1));
+    S->nt = nt;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int q = 0; q < nq; ++q) {
         li_quad* Q = &S->quads[q];
@@ -130,7 +179,7 @@ static int li_scene_build(li_scene* S, const float* quads, const int32_t* flip, 
         li_cross3(n, Q->e1, a2);
         const float s1 = li_dot3(Q->e1, a1), s2 = li_dot3(Q->e2, a2);
         for (int a = 0; a < 3; ++a) { Q->g1[a] = a1[a] / s1; Q->g2[a] = a2[a] / s2; }
-        Q->bsdf = bsdf[q];
+        Q->bsdf = bsdf ? bsdf[q] : 0;
         Q->emitter = emitter ? emitter[q] : -1;
         for (int c = 0; c < 4; ++c)
             for (int a = 0; a < 3; ++a) {
@@ -139,10 +188,42 @@ static int li_scene_build(li_scene* S, const float* quads, const int32_t* flip, 
                 mx[a] = fmaxf(mx[a], x);
             }
     }
+    if (nt > 0)
+        for (int i = 0; i < nverts; ++i)
+            for (int a = 0; a < 3; ++a) {
+                mn[a] = fminf(mn[a], verts[3 * i + a]);
+                mx[a] = fmaxf(mx[a], verts[3 * i + a]);
+            }
+    for (int i = 0; i < nt; ++i) {
+        li_tri* T = &S->tris[i];
+        for (int k = 0; k < 3; ++k)
+            if (tri[3 * i + k] < 0 || tri[3 * i + k] >= nverts) return 0;
+        const float *p0 = verts + 3 * tri[3 * i], *p1 = verts + 3 * tri[3 * i + 1], *p2 = verts + 3 * tri[3 * i + 2];
+        for (int a = 0; a < 3; ++a) { T->p0[a] = p0[a]; T->e1[a] = p1[a] - p0[a]; T->e2[a] = p2[a] - p0[a]; }
+        float n[3];
+        li_cross3(T->e1, T->e2, n);
+        const float len = sqrtf(li_dot3(n, n));
+        if (!(len > 0.0f)) return 0;
+        const float sg = (tri_flip && tri_flip[i]) ? -1.0f : 1.0f;
+        for (int a = 0; a < 3; ++a) T->n[a] = sg * n[a] / len;
+        T->bsdf = tri_bsdf ? tri_bsdf[i] : 0;
+        T->emitter = tri_emitter ? tri_emitter[i] : -1;
+    }
     float norm = 0.0f;
     for (int a = 0; a < 3; ++a) norm = fmaxf(norm, mx[a] - mn[a]);
     for (int a = 0; a < 3; ++a) S->smin[a] = mn[a];
     S->snorm = norm;
+    return 1;
+}
+
+static int li_scene_build(li_scene* S, const float* quads, const int32_t* flip, const int32_t* bsdf, int nq,
+                          const float* refl, const float* bpar, const int32_t* emitter, const float* rad,
+                          const float cam[16], float fov, float near_clip, int width, int height, const float* verts,
+                          int nverts, const int32_t* tri, int nt, const int32_t* tri_bsdf,
+                          const int32_t* tri_emitter, const int32_t* tri_flip) {
+    if (!li_geometry_build(S, quads, flip, bsdf, nq, emitter, verts, nverts, tri, nt, tri_bsdf, tri_emitter,
+                           tri_flip))
+        return 0;
     S->refl = refl;
     S->bpar = bpar;
     S->rad = rad;
@@ -156,7 +237,32 @@ static int li_scene_build(li_scene* S, const float* quads, const int32_t* flip, 
     return 1;
 }
 
-/* closest hit with t in (mint, maxt) */
+/* Triangle::rayIntersect (include/mitsuba/core/triangle.h:109-145): pvec = d x
+ * e2, det = e1 . pvec (0: no hit), u = (tvec . pvec) / det in [0, 1], qvec =
+ * tvec x e1, v = (d . qvec) / det >= 0 with u + v <= 1, t = (e2 . qvec) / det
+ * -- each "/ det" a product with inv_det = 1 / det, as there */
+static int li_tri_intersect(const li_tri* T, const float o[3], const float d[3], float* t) {
+    float pvec[3], qvec[3];
+    li_cross3(d, T->e2, pvec);
+    const float det = li_dot3(T->e1, pvec);
+    if (det == 0.0f) return 0;
+    const float inv_det = 1.0f / det;
+    const float tvec[3] = {o[0] - T->p0[0], o[1] - T->p0[1], o[2] - T->p0[2]};
+    const float u = li_dot3(tvec, pvec) * inv_det;
+    if (u < 0.0f || u > 1.0f) return 0;
+    li_cross3(tvec, T->e1, qvec);
+    const float v = li_dot3(d, qvec) * inv_det;
+    if (v >= 0.0f && u + v <= 1.0f) {
+        *t = li_dot3(T->e2, qvec) * inv_det;
+        return 1;
+    }
+    return 0;
+}
+
+/* closest hit with t in (mint, maxt): the smallest t wins, on exactly equal t
+ * the lowest primitive id -- every quad before every triangle.  Both loops
+ * visit the ids in ascending order, so the strict t < tb alone keeps the
+ * lowest id of a tie.  All the triangles in a loop: no traversal to get wrong. */
 static int li_intersect(const li_scene* S, const float o[3], const float d[3], float mint, float maxt, float* t_hit) {
     int best = -1;
     float tb = maxt;
@@ -173,8 +279,40 @@ static int li_intersect(const li_scene* S, const float o[3], const float d[3], f
         tb = t;
         best = q;
     }
+    for (int i = 0; i < S->nt; ++i) {
+        float t;
+        if (!li_tri_intersect(&S->tris[i], o, d, &t)) continue;
+        if (!(t > mint && t < maxt)) continue;
+        if (t < tb) {
+            tb = t;
+            best = S->nq + i;
+        }
+    }
     *t_hit = tb;
     return best;
+}
+/* the hit primitive's normal, BSDF and emitter */
+static const float* li_prim_n(const li_scene* S, int q) { return q >= S->nq ? S->tris[q - S->nq].n : S->quads[q].n; }
+static int li_prim_bsdf(const li_scene* S, int q) { return q >= S->nq ? S->tris[q - S->nq].bsdf : S->quads[q].bsdf; }
+static int li_prim_emitter(const li_scene* S, int q) {
+    return q >= S->nq ? S->tris[q - S->nq].emitter : S->quads[q].emitter;
+}
+
+/* ctypes entry for the tests: the closest hit of nr rays (o, d: nr x 3)
+ * against the quads and the mesh; prim -1 and t = maxt without a hit */
+int or_li_intersect(const float* quads, const int32_t* flip, int n_quads, const float* verts, int n_verts,
+                    const int32_t* tri, int n_tris, int64_t nr, const float* o, const float* d, float mint,
+                    float maxt, int32_t* prim, float* t) {
+    FTZ_SCOPE;
+    li_scene S;
+    memset(&S, 0, sizeof(S));
+    const int ok = li_geometry_build(&S, quads, flip, NULL, n_quads, NULL, verts, n_verts, tri, n_tris, NULL, NULL,
+                                     NULL);
+    if (ok)
+        for (int64_t r = 0; r < nr; ++r) prim[r] = li_intersect(&S, o + 3 * r, d + 3 * r, mint, maxt, &t[r]);
+    free(S.quads);
+    free(S.tris);
+    return ok ? 0 : -1;
 }
 
 /* fresnelDielectricExt (libcore/util.cpp:651-681), the reflectance */
@@ -655,6 +793,178 @@ void or_bsdf_phong(const float* bp, const float rho[3], const float wi[3], const
     if (wo_eval) *e_pdf = li_phong_eval_pdf(wi, wo_eval, bp, rho, e_f);
 }
 
+/* ---- rough dielectric (bsdfs/roughdielectric.cpp over microfacet.h), local
+ * frame, bsdf kind 4: isotropic Beckmann, sampleVisible = false, both
+ * components, ERadiance.  bp: [1..3] specularReflectance, [4] eta = intIOR /
+ * extIOR, [5] 1 / eta, [6] alpha; st: specularTransmittance (the BSDF's
+ * reflectance row).  wi.z < 0 is a hit from inside.  The library's numeric
+ * contract: float in and out, double in between without contraction, exp / log
+ * / sincos in double, each result rounded to float once; the reference's float
+ * constants (1e-20f, smithG1's coefficients) keep their float values. ---- */
+extern void sincos(double x, double* s, double* c);
+#define LID_PI 3.14159265358979323846
+static double lid_dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+/* fresnelDielectricExt with cosThetaT (libcore/util.cpp:651-681), eta != 1:
+ * cos_t signed against cos_i, 0 at a total internal reflection */
+static double lid_fresnel(double cos_i, double eta, double* cos_t) {
+    const double scale = cos_i > 0.0 ? 1.0 / eta : eta;
+    const double ct2 = 1.0 - (1.0 - cos_i * cos_i) * (scale * scale);
+    if (ct2 <= 0.0) {
+        *cos_t = 0.0;
+        return 1.0;
+    }
+    const double ci = fabs(cos_i), ct = sqrt(ct2);
+    const double rs = (ci - eta * ct) / (ci + eta * ct);
+    const double rp = (eta * ci - ct) / (eta * ci + ct);
+    *cos_t = cos_i > 0.0 ? -ct : ct;
+    return 0.5 * (rs * rs + rp * rp);
+}
+/* MicrofacetDistribution::eval, Beckmann (microfacet.h:191-233) */
+static double lid_beckmann_d(const double m[3], double alpha) {
+    if (m[2] <= 0.0) return 0.0;
+    const double ct2 = m[2] * m[2];
+    const double ex = ((m[0] * m[0]) / (alpha * alpha) + (m[1] * m[1]) / (alpha * alpha)) / ct2;
+    double r = exp(-ex) / (LID_PI * alpha * alpha * ct2 * ct2);
+    if (r * m[2] < (double)1e-20f) r = 0.0;
+    return r;
+}
+/* smithG1 (microfacet.h:477-518) */
+static double lid_beckmann_g1(const double v[3], const double m[3], double alpha) {
+    if (lid_dot3(v, m) * v[2] <= 0.0) return 0.0;
+    const double tmp = 1.0 - v[2] * v[2];
+    const double tan_t = tmp <= 0.0 ? 0.0 : fabs(sqrt(tmp) / v[2]);
+    if (tan_t == 0.0) return 1.0;
+    const double a = 1.0 / (alpha * tan_t);
+    if (a >= (double)1.6f) return 1.0;
+    const double a2 = a * a;
+    return ((double)3.535f * a + (double)2.181f * a2) / (1.0 + (double)2.276f * a + (double)2.577f * a2);
+}
+/* sampleAll (microfacet.h:287-395): the microfacet normal of (u0, u1), its density (0 below 1e-20) */
+static double lid_beckmann_sample(double alpha, double u0, double u1, double m[3]) {
+    const double phi = (2.0 * LID_PI) * u1;
+    double sp, cp;
+    sincos(phi, &sp, &cp);
+    const double a2 = alpha * alpha;
+    const double tan2 = a2 * -log(1.0 - u0);
+    const double ct = 1.0 / sqrt(1.0 + tan2);
+    double mpdf = (1.0 - u0) / (LID_PI * alpha * alpha * ct * ct * ct);
+    if (mpdf < (double)1e-20f) mpdf = 0.0;
+    const double st = sqrt(fmax(0.0, 1.0 - ct * ct));
+    m[0] = st * cp; m[1] = st * sp; m[2] = ct;
+    return mpdf;
+}
+/* the Walter trick (roughdielectric.cpp:453-458, :492-498): the sampling distribution's alpha */
+static double lid_sample_alpha(double alpha, double cos_i) { return alpha * (1.2 - 0.2 * sqrt(fabs(cos_i))); }
+/* bRec.eta as sample sets it (:615, :633) for a given pair of directions: 1
+ * on reflection, eta entering (wi.z > 0), 1 / eta leaving */
+static float li_roughdielectric_crossed(const float wi[3], const float wo[3], const float* bp) {
+    if ((double)wi[2] * (double)wo[2] > 0.0) return 1.0f;
+    return wi[2] > 0.0f ? bp[4] : bp[5];
+}
+/* RoughDielectric::eval (ESolidAngle, :317-395) into f; returns RoughDielectric::pdf
+ * (:397-469).  wo on either side; wi.z == 0: both 0 (:318). */
+static float li_roughdielectric_eval_pdf(const float wi_[3], const float wo_[3], const float* bp, const float st[3],
+                                         float f[3]) {
+    f[0] = f[1] = f[2] = 0.0f;
+    if (wi_[2] == 0.0f) return 0.0f;
+    const double wi[3] = {wi_[0], wi_[1], wi_[2]}, wo[3] = {wo_[0], wo_[1], wo_[2]};
+    const double eta = bp[4], inv_eta = bp[5], alpha = bp[6];
+    const int reflect = wi[2] * wo[2] > 0.0;
+    const double e = wi[2] > 0.0 ? eta : inv_eta;
+    double hs[3], H[3];
+    for (int a = 0; a < 3; ++a) hs[a] = reflect ? wo[a] + wi[a] : wi[a] + wo[a] * e;   /* :340-349 */
+    const double rc = 1.0 / sqrt(hs[0] * hs[0] + hs[1] * hs[1] + hs[2] * hs[2]);
+    for (int a = 0; a < 3; ++a) H[a] = hs[a] * rc;
+    if (copysign(1.0, H[2]) < 0.0)                                                     /* H *= signum(cosTheta(H)) */
+        for (int a = 0; a < 3; ++a) H[a] = -H[a];
+    const double wi_h = lid_dot3(wi, H), wo_h = lid_dot3(wo, H);
+    double cos_t;
+    const double F = lid_fresnel(wi_h, eta, &cos_t);
+    const double sqrt_denom = wi_h + e * wo_h;
+    const double D = lid_beckmann_d(H, alpha);
+    if (D != 0.0) {
+        const double G = lid_beckmann_g1(wi, H, alpha) * lid_beckmann_g1(wo, H, alpha);
+        if (reflect) {
+            const double value = F * D * G / (4.0 * fabs(wi[2]));                      /* :373-377 */
+            for (int ch = 0; ch < 3; ++ch) f[ch] = (float)((double)bp[1 + ch] * value);
+        } else {
+            const double value = ((1.0 - F) * D * G * e * e * wi_h * wo_h) / (wi[2] * sqrt_denom * sqrt_denom);
+            const double factor = wi[2] > 0.0 ? inv_eta : eta;                         /* ERadiance (:389-393) */
+            const double v = fabs(value * factor * factor);
+            for (int ch = 0; ch < 3; ++ch) f[ch] = (float)((double)st[ch] * v);
+        }
+    }
+    const double dwh_dwo = reflect ? 1.0 / (4.0 * wo_h) : (e * e * wo_h) / (sqrt_denom * sqrt_denom);
+    double prob = lid_beckmann_d(H, lid_sample_alpha(alpha, wi[2])) * H[2];
+    prob *= reflect ? F : (1.0 - F);
+    return (float)fabs(prob * dwh_dwo);
+}
+/* RoughDielectric::sample(bRec, pdf, sample) (:560-662); u2: the sampler's
+ * next1D() for the lobe, reflection when u2 <= F.  0: void (weight 0, pdf 0,
+ * eta 1; wo as far as it was formed) -- microfacet pdf 0, a failed side check,
+ * cosThetaT == 0 (refract, libcore/util.cpp:767-772), wi.z == 0. */
+static int li_roughdielectric_sample(const float wi_[3], const float* bp, const float st[3], float u0, float u1,
+                                     float u2, float wo_[3], float bw[3], float* pdf, float* eta_out) {
+    const double eta = bp[4], inv_eta = bp[5], alpha = bp[6];
+    *pdf = 0.0f;
+    *eta_out = 1.0f;
+    bw[0] = bw[1] = bw[2] = 0.0f;
+    wo_[0] = 0.0f; wo_[1] = 0.0f; wo_[2] = 1.0f;
+    if (wi_[2] == 0.0f) return 0;
+    const double wi[3] = {wi_[0], wi_[1], wi_[2]};
+    double m[3], wo[3];
+    const double mpdf = lid_beckmann_sample(lid_sample_alpha(alpha, wi[2]), (double)u0, (double)u1, m);
+    if (mpdf == 0.0) return 0;
+    const double dm = lid_dot3(wi, m);
+    double cos_t;
+    const double F = lid_fresnel(dm, eta, &cos_t);
+    const int reflect = (double)u2 <= F;
+    double p, dwh_dwo, scale = 1.0;
+    float crossed = 1.0f;
+    const float* tint;
+    if (reflect) {
+        p = mpdf * F;
+        for (int a = 0; a < 3; ++a) wo[a] = 2.0 * dm * m[a] - wi[a];
+        for (int a = 0; a < 3; ++a) wo_[a] = (float)wo[a];
+        if (wi[2] * wo[2] <= 0.0 || wo_[2] == 0.0f) return 0;
+        tint = bp + 1;
+        dwh_dwo = 1.0 / (4.0 * lid_dot3(wo, m));
+    } else {
+        p = mpdf * (1.0 - F);
+        if (cos_t == 0.0) return 0;
+        const double er = cos_t < 0.0 ? inv_eta : eta;     /* refract(wi, m, eta, cosThetaT) */
+        const double k = dm * er + cos_t;
+        for (int a = 0; a < 3; ++a) wo[a] = m[a] * k - wi[a] * er;
+        for (int a = 0; a < 3; ++a) wo_[a] = (float)wo[a];
+        crossed = cos_t < 0.0 ? bp[4] : bp[5];
+        if (wi[2] * wo[2] >= 0.0 || wo_[2] == 0.0f) return 0;
+        const double factor = cos_t < 0.0 ? inv_eta : eta;
+        tint = st;
+        scale = factor * factor;
+        const double wo_m = lid_dot3(wo, m), ce = (double)crossed;
+        const double sqrt_denom = dm + ce * wo_m;
+        dwh_dwo = (ce * ce * wo_m) / (sqrt_denom * sqrt_denom);
+    }
+    const double g = lid_beckmann_g1(wi, m, alpha) * lid_beckmann_g1(wo, m, alpha);
+    const double weight = fabs(lid_beckmann_d(m, alpha) * g * dm / (mpdf * wi[2]));
+    for (int ch = 0; ch < 3; ++ch) bw[ch] = (float)(((double)tint[ch] * scale) * weight);
+    *pdf = (float)fabs(p * dwh_dwo);
+    *eta_out = crossed;
+    return 1;
+}
+/* ctypes entry for the tests: u (3) given -> the sample (s_wo, s_weight,
+ * s_pdf, eta); wo_eval given -> eval, pdf and the crossed index there */
+void or_bsdf_roughdielectric(const float* bp, const float st[3], const float wi[3], const float* u,
+                             const float* wo_eval, float s_wo[3], float s_weight[3], float* s_pdf, float e_f[3],
+                             float* e_pdf, float* eta_out) {
+    FTZ_SCOPE;
+    if (u) li_roughdielectric_sample(wi, bp, st, u[0], u[1], u[2], s_wo, s_weight, s_pdf, eta_out);
+    if (wo_eval) {
+        *e_pdf = li_roughdielectric_eval_pdf(wi, wo_eval, bp, st, e_f);
+        *eta_out = li_roughdielectric_crossed(wi, wo_eval, bp);
+    }
+}
+
 typedef struct {
     const li_scene* S;
     const float *mn, *mx;
@@ -674,6 +984,9 @@ typedef struct {
     float* L;        /* P x 3 radiance */
     int32_t* comps;  /* bounces x P */
     int32_t* hit_bsdf;   /* bounces x P, optional: the BSDF a live bounce scattered at (-1: none) */
+    int32_t* inside;     /* bounces x P, optional: 1 a live bounce met its surface from behind (wi . n < 0), 0
+                            from the front, -1 no live bounce */
+    int rr_eta_one;      /* tests only: roulette with the path's relative index taken as 1 */
     int bounces;
 } li_job;
 
@@ -751,36 +1064,44 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
     int q = li_intersect(S, o, d, S->near_clip / l[2], INFINITY, &t);
     float thr[3] = {1.0f, 1.0f, 1.0f}, Li[3] = {0.0f, 0.0f, 0.0f}, p[3] = {0.0f, 0.0f, 0.0f};
     int nv = 0;
+    float eta = 1.0f;   /* the path's relative index (:604) */
     if (q >= 0) {
-        const li_quad* Q = &S->quads[q];
+        const int qe = li_prim_emitter(S, q);
         for (int a = 0; a < 3; ++a) p[a] = o[a] + t * d[a];
-        if (Q->emitter >= 0 && -li_dot3(d, Q->n) > 0.0f)
-            for (int ch = 0; ch < 3; ++ch) Li[ch] = S->rad[3 * Q->emitter + ch];
+        if (qe >= 0 && -li_dot3(d, li_prim_n(S, q)) > 0.0f)
+            for (int ch = 0; ch < 3; ++ch) Li[ch] = S->rad[3 * qe + ch];
     }
     int depth = q >= 0 ? 1 : -1;
     for (int b = 0; b < J->bounces; ++b) {
-        int32_t comp_out = -9, bsdf_out = -1;
+        int32_t comp_out = -9, bsdf_out = -1, inside_out = -1;
         if (depth >= 0) {
             /* loop head (:684-691), sampleSurface (:275-421) */
             int live = !(J->max_depth >= 0 && depth >= J->max_depth);
-            const li_quad* QD = &S->quads[q];
-            const float* n = QD->n;
-            const float* rho = S->refl + 3 * QD->bsdf;
-            const float* bp = S->bpar ? S->bpar + 8 * QD->bsdf : NULL;
+            const int qbsdf = li_prim_bsdf(S, q);
+            const float* n = li_prim_n(S, q);
+            const float* rho = S->refl + 3 * qbsdf;
+            const float* bp = S->bpar ? S->bpar + 8 * qbsdf : NULL;
             const int plastic = bp && bp[0] == 1.0f;
             const int conductor = bp && bp[0] == 2.0f;
             const int phong = bp && bp[0] == 3.0f;
-            const int zero_spec =
-                !(plastic || conductor || phong) || (bp[1] == 0.0f && bp[2] == 0.0f && bp[3] == 0.0f);
+            const int dielectric = bp && bp[0] == 4.0f;
+            const int zero_spec = !(plastic || conductor || phong || dielectric) ||
+                                  (bp[1] == 0.0f && bp[2] == 0.0f && bp[3] == 0.0f);
+            /* (a dielectric's reflectance row is its specularTransmittance) */
             const int zero_diff = conductor || (rho[0] == 0.0f && rho[1] == 0.0f && rho[2] == 0.0f);
             const float wi[3] = {-d[0], -d[1], -d[2]};
-            if (live && (!(li_dot3(wi, n) > 0.0f) || (zero_diff && zero_spec)))
+            /* a rough dielectric scatters from either side: it is dead only at wi . n == 0 */
+            const float cos_i = li_dot3(wi, n);
+            const int side = dielectric ? (cos_i > 0.0f || cos_i < 0.0f) : cos_i > 0.0f;
+            const int inside = dielectric && cos_i < 0.0f;   /* cosTheta(bRec.wi) < 0 */
+            if (live && (!side || (zero_diff && zero_spec)))
                 live = 0;
             if (!live) {
                 depth = -1;
             } else {
                 const uint32_t stream = 1u + (uint32_t)b;
-                bsdf_out = QD->bsdf;
+                bsdf_out = qbsdf;
+                inside_out = cos_i < 0.0f ? 1 : 0;
                 const float c[3] = {(p[0] - S->smin[0]) / S->snorm, (p[1] - S->smin[1]) / S->snorm,
                                     (p[2] - S->smin[2]) / S->snorm};
                 float s[3], tt[3], w[3];
@@ -788,6 +1109,7 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                 /* the BSDF sample (plastic: SmoothPlastic::sample, plastic.cpp:378-420) */
                 int delta = 0;
                 float bw[3] = {0.0f, 0.0f, 0.0f}, bpdf = 0.0f, Fi = 0.0f, ps = 0.0f;
+                float bcrossed = 1.0f;   /* bRec.eta of the BSDF sample */
                 if (plastic) {
                     const float wl[3] = {li_dot3(wi, s), li_dot3(wi, tt), li_dot3(wi, n)};
                     Fi = li_fresnel(wl[2], bp[4]);
@@ -815,6 +1137,13 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                     const float wl[3] = {li_dot3(wi, s), li_dot3(wi, tt), li_dot3(wi, n)};
                     li_phong_sample(wl, bp, rho, or_rng_uniform(J->seed, gp, stream, 0),
                                     or_rng_uniform(J->seed, gp, stream, 1), w, bw, &bpdf);
+                } else if (dielectric) {
+                    /* Frame(n) of the stored normal whatever the side; the lobe's uniform
+                     * (sampler->next1D(), roughdielectric.cpp:601) is dimension 7 */
+                    const float wl[3] = {li_dot3(wi, s), li_dot3(wi, tt), li_dot3(wi, n)};
+                    li_roughdielectric_sample(wl, bp, rho, or_rng_uniform(J->seed, gp, stream, 0),
+                                              or_rng_uniform(J->seed, gp, stream, 1),
+                                              or_rng_uniform(J->seed, gp, stream, 7), w, bw, &bpdf, &bcrossed);
                 } else {
                     li_cosine_hemisphere(or_rng_uniform(J->seed, gp, stream, 0),
                                          or_rng_uniform(J->seed, gp, stream, 1), w);
@@ -838,7 +1167,7 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                         int glossy = 0;
                         if (conductor && J->product) {
                             const float wl[3] = {li_dot3(wi, s), li_dot3(wi, tt), li_dot3(wi, n)};
-                            const float* lm = J->S->lmodel ? J->S->lmodel + (size_t)LI_L4_STRIDE * QD->bsdf : NULL;
+                            const float* lm = J->S->lmodel ? J->S->lmodel + (size_t)LI_L4_STRIDE * qbsdf : NULL;
                             const int LM = lm ? (int)lm[0] : 0;
                             int kept = 0;
                             if (LM > 0)
@@ -852,7 +1181,7 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                              * component kept */
                             const float wl[3] = {li_dot3(wi, s), li_dot3(wi, tt), li_dot3(wi, n)};
                             const float* lm =
-                                J->S->lmodel_nd ? J->S->lmodel_nd + (size_t)LI_ND_STRIDE * QD->bsdf : NULL;
+                                J->S->lmodel_nd ? J->S->lmodel_nd + (size_t)LI_ND_STRIDE * qbsdf : NULL;
                             const int LM = lm ? (int)lm[1] : 0;
                             int kept = 0;
                             if (LM > 0) {
@@ -863,8 +1192,24 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                             }
                             for (int l = kept; l < J->lM; ++l) gw[l] = 0.0f;
                             glossy = kept > 0 ? 1 : -1;
+                        } else if (dielectric && J->product) {
+                            /* RoughDielectric::getDMM (roughdielectric.cpp:198-211): none from
+                             * inside (cosTheta(wi) <= 0, :199); else the SDMM5 at (theta_i, alpha,
+                             * eta), pruned to 2, no forced component */
+                            const float wl[3] = {li_dot3(wi, s), li_dot3(wi, tt), li_dot3(wi, n)};
+                            const float* lm =
+                                J->S->lmodel_nd ? J->S->lmodel_nd + (size_t)LI_ND_STRIDE * qbsdf : NULL;
+                            const int LM = lm ? (int)lm[1] : 0;
+                            int kept = 0;
+                            if (LM > 0 && wl[2] > 0.0f) {
+                                const float x[3] = {fl_acos(fminf(1.0f, wl[2])), bp[6], bp[4]};
+                                kept = li_learned_nd_conditional(lm + 2, (int)lm[0], LM, x, wl, LI_L4_KEEP, -1, gw, gm,
+                                                                 gc);
+                            }
+                            for (int l = kept; l < J->lM; ++l) gw[l] = 0.0f;
+                            glossy = kept > 0 ? 1 : -1;
                         }
-                        comp = li_guide_query(J, m, cd, pr, c, u, bdir, mode_bsdf, choice, QD->bsdf, F, glossy, gw,
+                        comp = li_guide_query(J, m, cd, pr, c, u, bdir, mode_bsdf, choice, qbsdf, F, glossy, gw,
                                               gm, gc, gd, &gpdf, &hq);
                         if (J->product && comp != -1) h = hq;
                     }
@@ -873,6 +1218,7 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                 /* the rest of sampleSurface / pdfSurface (:392-507, :587-589) */
                 float wo[3], weight[3], mis_pdf;
                 int cacheable = 1;
+                float crossed = 1.0f;   /* bRec.eta of the direction taken */
                 if (plastic && comp != -1 && comp != -2) {
                     /* the guide's direction: the smooth lobe's eval / pdfSurface */
                     wo[0] = gd[0]; wo[1] = gd[1]; wo[2] = gd[2];
@@ -903,9 +1249,10 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                         mis_pdf = bpdf > 0.0f ? h * bpdf + (1.0f - h) * gpdf : 0.0f;
                         for (int ch = 0; ch < 3; ++ch) weight[ch] = mis_pdf == 0.0f ? 0.0f : (bw[ch] * bpdf) * (1.0f / mis_pdf);
                     }
-                } else if (conductor || phong) {
+                } else if (conductor || phong || dielectric) {
                     if (comp == -1 || comp == -2) {
                         wo[0] = bdir[0]; wo[1] = bdir[1]; wo[2] = bdir[2];
+                        crossed = bcrossed;
                         if (comp == -1) {
                             mis_pdf = bpdf;
                             for (int ch = 0; ch < 3; ++ch) weight[ch] = bw[ch];
@@ -920,9 +1267,13 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                         const float wol[3] = {li_dot3(wo, s), li_dot3(wo, tt), li_dot3(wo, n)};
                         const int zero = (wo[0] == 0.0f && wo[1] == 0.0f && wo[2] == 0.0f) || !isfinite(wol[2]);
                         float f[3] = {0.0f, 0.0f, 0.0f};
-                        const float bsdf_pdf = zero    ? 0.0f
-                                               : phong ? li_phong_eval_pdf(wil, wol, bp, rho, f)
-                                                       : li_conductor_eval_pdf(wil, wol, bp, f);
+                        /* (a dielectric: over the whole sphere; bRec.eta is what sample would
+                         * have set for this direction -- eval leaves it unset) */
+                        const float bsdf_pdf = zero         ? 0.0f
+                                               : phong      ? li_phong_eval_pdf(wil, wol, bp, rho, f)
+                                               : dielectric ? li_roughdielectric_eval_pdf(wil, wol, bp, rho, f)
+                                                            : li_conductor_eval_pdf(wil, wol, bp, f);
+                        if (dielectric) crossed = li_roughdielectric_crossed(wil, wol, bp);
                         mis_pdf = bsdf_pdf > 0.0f ? h * bsdf_pdf + (1.0f - h) * gpdf : 0.0f;
                         for (int ch = 0; ch < 3; ++ch) weight[ch] = mis_pdf == 0.0f ? 0.0f : f[ch] * (1.0f / mis_pdf);
                     }
@@ -956,9 +1307,9 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                     const int qh = li_intersect(S, oo, wo, kEps, INFINITY, &th);
                     float value[3] = {0.0f, 0.0f, 0.0f};
                     if (qh >= 0) {
-                        const li_quad* H = &S->quads[qh];
-                        if (H->emitter >= 0 && -li_dot3(wo, H->n) > 0.0f)
-                            for (int ch = 0; ch < 3; ++ch) value[ch] = S->rad[3 * H->emitter + ch];
+                        const int he = li_prim_emitter(S, qh);
+                        if (he >= 0 && -li_dot3(wo, li_prim_n(S, qh)) > 0.0f)
+                            for (int ch = 0; ch < 3; ++ch) value[ch] = S->rad[3 * he + ch];
                     }
                     if (value[0] != 0.0f || value[1] != 0.0f || value[2] != 0.0f) {
                         const float radv[3] = {thr[0] * value[0], thr[1] * value[1], thr[2] * value[2]};
@@ -982,13 +1333,17 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                         for (int a = 0; a < 3; ++a) {
                             LI_REC(J, 7 + a, nv, i) = c[a];
                             LI_REC(J, 10 + a, nv, i) = wo[a];
-                            LI_REC(J, 13 + a, nv, i) = n[a];
+                            /* inside the medium the vertex carries -n (:765-767) */
+                            LI_REC(J, 13 + a, nv, i) = inside ? -n[a] : n[a];
                         }
                         ++nv;
                     }
                     int alive = qh >= 0;
+                    eta = eta * crossed;   /* eta *= bRec.eta (:788) */
                     if (depth >= J->rr_depth && alive) {   /* Russian roulette (:858-868) */
-                        const float qq = fminf(fmaxf(thr[0], fmaxf(thr[1], thr[2])), 0.95f);
+                        /* q = min(throughput.max() * eta * eta, 0.95) (:864) */
+                        const float re = J->rr_eta_one ? 1.0f : eta;
+                        const float qq = fminf(fmaxf(thr[0], fmaxf(thr[1], thr[2])) * re * re, 0.95f);
                         if (or_rng_uniform(J->seed, gp, 1u + (uint32_t)b, 6) >= qq) alive = 0;
                         else for (int ch = 0; ch < 3; ++ch) thr[ch] /= qq;
                     }
@@ -1003,6 +1358,7 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
         }
         if (J->comps) J->comps[(int64_t)b * J->P + i] = comp_out;
         if (J->hit_bsdf) J->hit_bsdf[(int64_t)b * J->P + i] = bsdf_out;
+        if (J->inside) J->inside[(int64_t)b * J->P + i] = inside_out;
     }
     J->nv[i] = nv;
     for (int ch = 0; ch < 3; ++ch) J->L[3 * i + ch] = Li[ch];
@@ -1037,12 +1393,17 @@ int or_li_render(const float* quads, const int32_t* flip, const int32_t* bsdf, i
                  int64_t pix_end, int product, const float* bw, const float* bmean, const float* bcov,
                  const uint8_t* bdiff, int M, int Kmax, float* image, float* image_sqr, float* rec, int32_t* nv,
                  int32_t* comps, int nthreads, const float* learned_models, const float* learned_models_nd,
-                 int32_t* hit_bsdf) {
+                 int32_t* hit_bsdf, const float* mesh_vertices, int n_mesh_vertices, const int32_t* triangles,
+                 int n_triangles, const int32_t* tri_bsdf, const int32_t* tri_emitter, const int32_t* tri_flip,
+                 int32_t* inside, int rr_eta_one) {
     FTZ_SCOPE;
     li_scene S;
+    memset(&S, 0, sizeof(S));
     if (!li_scene_build(&S, quads, flip, bsdf, n_quads, refl, bsdf_params, emitter, rad, cam, fov, near_clip, width,
-                        height)) {
+                        height, mesh_vertices, n_mesh_vertices, triangles, n_triangles, tri_bsdf, tri_emitter,
+                        tri_flip)) {
         free(S.quads);
+        free(S.tris);
         return -1;
     }
     S.lmodel = learned_models;   /* LI_L4_STRIDE floats per BSDF, NULL: none */
@@ -1056,16 +1417,18 @@ int or_li_render(const float* quads, const int32_t* flip, const int32_t* bsdf, i
     J.V = V; J.product = product; J.h = h; J.seed = seed;
     J.path0 = pix_begin * spp; J.P = P;
     J.bw = bw; J.bmean = bmean; J.bcov = bcov; J.bdiff = bdiff; J.M = M; J.Kmax = Kmax;
-    /* the device's rule (sdmm_scene_create: a conductor or a Phong BSDF on some
-     * quad, with or without a learned model, gives every compact query its own
-     * row of max(M, 2) lobes; extend_learned, render_api.cpp) */
+    /* the device's rule (sdmm_scene_create: a conductor, a Phong BSDF or a
+     * rough dielectric on some quad or triangle, with or without a learned
+     * model, gives every compact query its own row of max(M, 2) lobes;
+     * extend_learned, render_api.cpp) */
     J.lM = M;
     if (bsdf_params)
-        for (int q = 0; q < n_quads; ++q) {
-            const float kind = bsdf_params[8 * bsdf[q]];
-            if ((kind == 2.0f || kind == 3.0f) && J.lM < LI_L4_KEEP) J.lM = LI_L4_KEEP;
+        for (int q = 0; q < n_quads + n_triangles; ++q) {
+            const float kind = bsdf_params[8 * li_prim_bsdf(&S, q)];
+            if ((kind == 2.0f || kind == 3.0f || kind == 4.0f) && J.lM < LI_L4_KEEP) J.lM = LI_L4_KEEP;
         }
     J.rec = rec; J.nv = nv; J.comps = comps; J.hit_bsdf = hit_bsdf;
+    J.inside = inside; J.rr_eta_one = rr_eta_one;
     J.L = (float*)malloc(sizeof(float) * 3 * (size_t)(P > 0 ? P : 1));
     J.bounces = max_depth > 0 ? max_depth - 1 : V;
     if (nthreads < 1) nthreads = 1;
@@ -1099,5 +1462,6 @@ int or_li_render(const float* quads, const int32_t* flip, const int32_t* bsdf, i
     free(R);
     free(J.L);
     free(S.quads);
+    free(S.tris);
     return 0;
 }

@@ -211,9 +211,11 @@ def _rel(got, ref):
     return np.abs(got - ref) / np.maximum(np.abs(ref), 1e-30)
 
 
-@pytest.mark.parametrize("alpha", [0.05, 0.2, 0.5])
-def test_host_matches_float64(pkg, scenes, alpha):
-    """wo, value, pdf and eta_out of the host's sample against the float64
+def check_matches_float64(make_bsdf, scenes, alpha, who="host"):
+    """The body of test_host_matches_float64 for any implementation with
+    HostBsdf's sample / eval (make_bsdf(bp, st)); returns the exempt share.
+
+    wo, value, pdf and eta_out of the host's sample against the float64
     sample of the same (wi, u), and its eval-mode call at the wo it returned
     against the float64 eval / pdf at that same float32 wo: rtol 1e-5 outside
     the three exempt conditions (<= 3 % of the pairs); at alpha 0.5 the bound
@@ -243,7 +245,7 @@ def test_host_matches_float64(pkg, scenes, alpha):
     eta64, alpha64 = float(bp[4]), float(bp[6])
     W = sphere_wi(rng, n)
     U = rng.uniform(0, 1, (n, 3)).astype(np.float32)
-    host = HostBsdf(pkg, bp, st)
+    host = make_bsdf(bp, st)
     got = [host.sample(w, u) for w, u in zip(W, U)]
     wo = np.float32([g[0] for g in got])
     val = np.float32([g[1] for g in got])
@@ -283,7 +285,7 @@ def test_host_matches_float64(pkg, scenes, alpha):
     worst32 = float(e_32[ok & ~ex32].max())
     bound = 1e-5 if alpha < 0.5 else max(1e-5, 4 * worst32)
     inside = int((W[:, 2] < 0).sum())
-    print(f"roughdielectric host alpha {alpha}: worst non-exempt rel err {worst:.3g} (bound {bound:.3g}; numpy "
+    print(f"roughdielectric {who} alpha {alpha}: worst non-exempt rel err {worst:.3g} (bound {bound:.3g}; numpy "
           f"float32 {worst32:.3g}), exempt {100 * share:.2f} %, reflected {int((refl & ok).sum())}, transmitted "
           f"{int((~refl & ok).sum())}, inside {inside}, void {int(lib_void.sum())}")
     wo_tol = 4e-6 + 5e-7 / np.maximum(st_m, 1e-30) + np.where(refl, 0.0, 1e-6 / np.maximum(np.abs(ct_m), 1e-30))
@@ -294,6 +296,14 @@ def test_host_matches_float64(pkg, scenes, alpha):
     assert (refl & ok).sum() > 300 and (~refl & ok).sum() > 1000 and inside > 2000 and lib_void.sum() > 5
     assert n - inside > 2000
     assert worst <= bound
+    return share
+
+
+@pytest.mark.parametrize("alpha", [0.05, 0.2, 0.5])
+def test_host_matches_float64(pkg, scenes, alpha):
+    """check_matches_float64 (above: inputs, tolerances, exemptions) on
+    sdmm_bsdf_roughdielectric_host."""
+    check_matches_float64(lambda bp, st: HostBsdf(pkg, bp, st), scenes, alpha)
 
 
 def _threshold(host, wi, u01):

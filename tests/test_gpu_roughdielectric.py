@@ -7,8 +7,9 @@ Cornell Box is unbiased against its BSDF-only render, trains bitwise like the
 host-routed oracle and saves inward normals inside the glass; Russian roulette
 with the relative index leaves the mean unchanged.
 
-The CPU Li oracle does not know the material yet: the dielectric bounce is
-pinned by these checks and not path by path."""
+The dielectric bounce is compared path by path with the CPU Li oracle in
+tests/test_gpu_li_oracle_dielectric.py (the oracle's own restatement of the
+material is pinned in tests/test_li_oracle_dielectric.py)."""
 import numpy as np
 import pytest
 
@@ -39,8 +40,11 @@ def _host_F(host, wi, u0, u1):
     return np.uint32(lo).view(np.float32)
 
 
-def test_batch_kernel_equals_host_bitwise(pkg, scenes, gpu):
-    import torch
+def edge_rows(pkg, scenes):
+    """The batch test's inputs: (rng, bp, st, host, W, U) -- 4099 rows of wi
+    over the whole sphere and uniforms with the edges placed by hand: wi.z of
+    0 and +-1e-4, inside hits beyond the critical angle, u0 of 0 and of the
+    largest float below 1, u2 == F and the next float above it."""
     rng = np.random.default_rng(4099)
     nq = 4099                                              # a tail in the last workgroup
     bp, st = params(scenes, 0.2, (0.9, 0.8, 0.7), (0.6, 0.95, 0.85))
@@ -64,6 +68,13 @@ def test_batch_kernel_equals_host_bitwise(pkg, scenes, gpu):
             U[i, 2] = F if i % 2 == 0 else np.nextafter(F, np.float32(2))
             n_tie += 1
     assert n_tie > 10 and (W[:, 2] < 0).sum() > 1500 and (W[:, 2] > 0).sum() > 1500
+    return rng, bp, st, host, W, U
+
+
+def test_batch_kernel_equals_host_bitwise(pkg, scenes, gpu):
+    import torch
+    rng, bp, st, host, W, U = edge_rows(pkg, scenes)
+    nq = len(W)
     dev = lambda a: [torch.from_numpy(np.ascontiguousarray(a[:, i])).to(gpu) for i in range(3)]
     wo_d, val_d, pdf_d, eta_d = pkg.bsdf_roughdielectric_device(bp, st, dev(W), u=dev(U))
     torch.cuda.synchronize()

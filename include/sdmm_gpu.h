@@ -108,6 +108,12 @@ int sdmm_layout(const sdmm_mix* m, int* resp_cpl, int* resp_lps, int* stats_cpl,
 /* Diagnostics: name of the kernel the handle launches for the responsibility
  * (which = 0) or statistics (which = 1) E-step; "" for a NULL handle. */
 const char* sdmm_kernel_name(const sdmm_mix* m, int which);
+/* Diagnostics: how many times the handle has built the coefficient image of
+ * its responsibility kernel (estep_resp_split_kernel reads one image per
+ * mixture; it is rebuilt by the first sdmm_responsibilities after a change of
+ * the parameters, not per call).  0 for handles that use another kernel or
+ * run with SDMM_RESP_IMAGE=inline. */
+int sdmm_resp_image_builds(const sdmm_mix* m, int64_t* count);
 /* Guided queries keep a per-query list of at most `cap` candidate components
  * (default 40, maximum 64); queries that do not fit take the full-K path.
  * Results are identical for every cap; 0 sends every query down the full-K

@@ -242,7 +242,7 @@ def stats_len(K: int) -> int:
 EXPORTED_SYMBOLS = [
     "sdmm_release_cached_scratch",
     "sdmm_em_params_default", "sdmm_create", "sdmm_destroy", "sdmm_num_components", "sdmm_layout",
-    "sdmm_kernel_name",
+    "sdmm_kernel_name", "sdmm_resp_image_builds",
     "sdmm_set_guide_capacity", "sdmm_set_guide_order", "sdmm_guide_fallback_count",
     "sdmm_set_stream", "sdmm_get_stream", "sdmm_synchronize", "sdmm_init_hemisphere",
     "sdmm_hemisphere_init_host", "sdmm_em_step", "sdmm_em_step_host", "sdmm_em_step_batched",
@@ -720,7 +720,16 @@ class SDMM:
         """E-step kernel layouts: (components per lane, lanes per sample)."""
         v = [C.c_int() for _ in range(4)]
         _check(lib().sdmm_layout(self.h, *[C.byref(x) for x in v]))
-        return {"resp": (v[0].value, v[1].value), "stats": (v[2].value, v[3].value)}
+        out = {"resp": (v[0].value, v[1].value), "stats": (v[2].value, v[3].value)}
+        # builder launches of the split kernel's coefficient image so far (an
+        # SDMM_LIB_PATH A/B library from before the image cache has no counter)
+        fn = getattr(lib(), "sdmm_resp_image_builds", None)
+        if fn is not None:
+            fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+            cnt = C.c_int64()
+            _check(fn(self.h, C.byref(cnt)))
+            out["resp_image_builds"] = cnt.value
+        return out
 
     def kernel_name(self, which: str = "resp") -> str:
         """Name of the E-step kernel the handle launches ("resp" or "stats")."""

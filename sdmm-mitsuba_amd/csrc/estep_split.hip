@@ -34,8 +34,11 @@
 //     NORM5 exp(-q/2) is one FMA chain (pdf_pair).
 //
 // The B image of the whole mixture (R = Kp/16 blocks x 8 forms x 64 lanes x 16
-// B = R x 8 KB, 64 KB at K = 128) is built in LDS by each workgroup from the
-// E-step record and read as one ds_read_b128 per fragment, conflict-free.  The
+// B = R x 8 KB, 64 KB at K = 128) is built once per parameter change by
+// estep_resp_image_kernel into a global buffer of the handle, copied into LDS
+// by each workgroup and read as one ds_read_b128 per fragment, conflict-free
+// (SDMM_RESP_IMAGE=inline: every workgroup builds it from the E-step record
+// itself, as before the image was cached; the same bits either way).  The
 // D layout gives each lane one component (col = lane & 15) of four samples
 // (rows 4 (lane >> 4) + j); the nonlinear rest of the pair math (angle, exp,
 // pdf) runs packed over sample pairs (j, j+1), the posterior normaliser sums
@@ -353,10 +356,29 @@ __device__ __forceinline__ void dma_pair(uintptr_t a0, uintptr_t a1, unsigned ld
         : "memory");
 }
 
-template <int R, int WPB, int OCC>
-__global__ void __launch_bounds__(64 * WPB, OCC)
-estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev s, int64_t n, int64_t nwaves,
-                        float* __restrict__ resp) {
+// The coefficient image in the order of the LDS carve: the R * 8 * 64
+// fragments at (r * 8 + f) * 64 + lane, then the R * 4 detInv pi quads
+// (components 16 r + 4 g .. + 3 at r * 4 + g).  One thread per 16-B entry.
+__device__ __forceinline__ u4 image_entry(const float* __restrict__ ep, int Kp, int idx, int nc) {
+    const float o_scene[3] = {kOrigin, kOrigin, kOrigin};
+    if (idx < nc) return coef_frag(ep, Kp, idx >> 9, (idx >> 6) & 7, idx & 63, o_scene);
+    const float* d = ep + EP_DIPI * Kp + 4 * (idx - nc);
+    return __builtin_bit_cast(u4, f4{d[0], d[1], d[2], d[3]});
+}
+
+__global__ void __launch_bounds__(256) estep_resp_image_kernel(const float* __restrict__ ep, int Kp,
+                                                               u4* __restrict__ img) {
+    const int R = Kp / 16, nc = R * 8 * 64, nd = R * 4;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx < nc + nd) img[idx] = image_entry(ep, Kp, idx, nc);
+}
+
+// INLINE: the workgroup builds the image from ep (img unused); otherwise it
+// copies the prebuilt image img (estep_resp_image_kernel's, of this ep).
+template <int R, int WPB, bool INLINE>
+__device__ __forceinline__ void resp_split_body(const float* __restrict__ ep, const u4* __restrict__ img, int Kp, int K,
+                                                const SamplesDev& s, int64_t n, int64_t nwaves,
+                                                float* __restrict__ resp) {
     // one LDS block carved into: per wave the feature ring (kFeatSlots x 512 B;
     // first, so every LDS-DMA destination lies below 64 KB), the coefficient
     // image (R blocks x 8 forms x 64 lanes), detInv pi of components 16 r + 4 g
@@ -374,22 +396,30 @@ estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
     f4* const st = (f4*)(cimg + NC + ND + wid * NS);
     static_assert(WPB * NF + NC + ND + WPB * NS == NTOT && (R != 8 || NS == 256), "LDS carve: every region has storage");
 
-    const float o_scene[3] = {kOrigin, kOrigin, kOrigin};
-#ifdef SDMM_SPLIT_DIAG_NOIMAGE   // (diagnostic: a zero coefficient image -- results are not responsibilities)
-    for (int idx = threadIdx.x; idx < NC + ND; idx += 64 * WPB) cimg[idx] = u4{0u, 0u, 0u, 0u};
-#else
-    for (int idx = threadIdx.x; idx < NC; idx += 64 * WPB)
-        cimg[idx] = coef_frag(ep, Kp, idx >> 9, (idx >> 6) & 7, idx & 63, o_scene);
-    for (int i = threadIdx.x; i < ND; i += 64 * WPB) {
-        const float* d = ep + EP_DIPI * Kp + 4 * i;
-        dimg[i] = f4{d[0], d[1], d[2], d[3]};
+    // cimg and dimg are one run of NC + ND entries, in the image's order
+    if constexpr (INLINE) {
+        for (int idx = threadIdx.x; idx < NC + ND; idx += 64 * WPB) cimg[idx] = image_entry(ep, Kp, idx, NC);
+    } else {
+        // a straight copy: all of the thread's 16-B loads issued, then its LDS
+        // writes (the last trip is partial: its load is clamped, its write is not done)
+        constexpr int T = 64 * WPB, TRIPS = (NC + ND + T - 1) / T;
+        u4 v[TRIPS];
+#pragma unroll
+        for (int i = 0; i < TRIPS; ++i) {
+            const int idx = (int)threadIdx.x + i * T;
+            v[i] = img[idx < NC + ND ? idx : NC + ND - 1];
+        }
+#pragma unroll
+        for (int i = 0; i < TRIPS; ++i) {
+            const int idx = (int)threadIdx.x + i * T;
+            if (idx < NC + ND) cimg[idx] = v[i];
+        }
     }
-#endif
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
     // the launch's 16-sample tiles dealt round robin over its waves (one round
-    // of resident waves: each workgroup builds the coefficient image once):
+    // of resident waves: each workgroup fills its coefficient image once):
     // wave w serves tiles w, w + nwaves, ..., so the waves running at one time
     // write neighbouring 8-KB row blocks.  (A contiguous range per wave put the
     // 2048 waves' concurrent rows 256 KB apart -- the same HBM channel bits --
@@ -674,6 +704,21 @@ estep_resp_split_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev 
     wait_vm<0>();
 }
 
+template <int R, int WPB, int OCC>
+__global__ void __launch_bounds__(64 * WPB, OCC)
+estep_resp_split_kernel(const float* __restrict__ ep, const u4* __restrict__ img, int Kp, int K, SamplesDev s,
+                        int64_t n, int64_t nwaves, float* __restrict__ resp) {
+    resp_split_body<R, WPB, false>(ep, img, Kp, K, s, n, nwaves, resp);
+}
+
+// SDMM_RESP_IMAGE=inline: the A/B and bitwise-test variant
+template <int R, int WPB, int OCC>
+__global__ void __launch_bounds__(64 * WPB, OCC)
+estep_resp_split_inline_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev s, int64_t n, int64_t nwaves,
+                               float* __restrict__ resp) {
+    resp_split_body<R, WPB, true>(ep, nullptr, Kp, K, s, n, nwaves, resp);
+}
+
 // ---------------------------------------------------------------------------
 // Configurations (R = Kp / 16 blocks, waves per workgroup, waves per SIMD).
 // The B image takes R x 8 KB of LDS per workgroup.
@@ -699,10 +744,24 @@ static void split_cfg(int R, int /*variant*/, int* wpb, int* occ) {
 
 bool estep_resp_split_supported(int Kp) { return Kp % 16 == 0 && Kp / 16 <= 8 && (Kp / 16 & (Kp / 16 - 1)) == 0; }
 
+// bytes of the coefficient image of a Kp-component record
+size_t estep_resp_image_bytes(int Kp) { return (size_t)(Kp / 16) * (8 * 64 + 4) * 16; }
+
+// img = the image of ep, in stream order (one thread per 16-B entry)
+hipError_t launch_estep_resp_image(const float* ep, int Kp, void* img, hipStream_t st) {
+    if (!estep_resp_split_supported(Kp) || !img) return hipErrorInvalidValue;
+    const int entries = (Kp / 16) * (8 * 64 + 4);
+    hipLaunchKernelGGL(estep_resp_image_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, st, ep, Kp,
+                       (u4*)img);
+    return hipGetLastError();
+}
+
 // resident_waves: waves of this kernel the device holds at once (the launch
-// is one round of them, fewer when n has fewer tiles)
-hipError_t launch_estep_resp_split(int variant, const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
-                                   int64_t resident_waves, float* resp, hipStream_t st) {
+// is one round of them, fewer when n has fewer tiles).  img: the prebuilt
+// coefficient image of ep (launch_estep_resp_image), or NULL for the kernel
+// that builds it in every workgroup.
+hipError_t launch_estep_resp_split(int variant, const float* ep, const void* img, int Kp, int K, const SamplesDev& s,
+                                   int64_t n, int64_t resident_waves, float* resp, hipStream_t st) {
     if (!estep_resp_split_supported(Kp) || K > Kp || resident_waves <= 0) return hipErrorInvalidValue;
     const int R = Kp / 16;
     int wpb, occ;
@@ -714,8 +773,12 @@ hipError_t launch_estep_resp_split(int variant, const float* ep, int Kp, int K, 
     if (waves >= (int64_t)1 << 26) return hipErrorInvalidValue;
 #define X(RR, WW, OO)                                                                                          \
     if (R == RR && wpb == WW && occ == OO) {                                                                   \
-        hipLaunchKernelGGL((estep_resp_split_kernel<RR, WW, OO>), dim3((unsigned)blocks), dim3(64 * WW), 0, st, ep, \
-                           Kp, K, s, n, waves, resp);                                                          \
+        if (img)                                                                                               \
+            hipLaunchKernelGGL((estep_resp_split_kernel<RR, WW, OO>), dim3((unsigned)blocks), dim3(64 * WW), 0, st, \
+                               ep, (const u4*)img, Kp, K, s, n, waves, resp);                                  \
+        else                                                                                                   \
+            hipLaunchKernelGGL((estep_resp_split_inline_kernel<RR, WW, OO>), dim3((unsigned)blocks), dim3(64 * WW), \
+                               0, st, ep, Kp, K, s, n, waves, resp);                                           \
         return hipGetLastError();                                                                              \
     }
     SDMM_SPLIT_CONFIGS(X)
@@ -724,7 +787,7 @@ hipError_t launch_estep_resp_split(int variant, const float* ep, int Kp, int K, 
 }
 
 // resident waves per CU of the configuration
-hipError_t estep_resp_split_occupancy(int variant, int Kp, int* waves_per_cu) {
+hipError_t estep_resp_split_occupancy(int variant, int Kp, bool inline_image, int* waves_per_cu) {
     const int R = Kp / 16;
     int wpb, occ;
     split_cfg(R, variant, &wpb, &occ);
@@ -732,7 +795,10 @@ hipError_t estep_resp_split_occupancy(int variant, int Kp, int* waves_per_cu) {
 #define X(RR, WW, OO)                                                                                          \
     if (R == RR && wpb == WW && occ == OO) {                                                                   \
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(                                           \
-            &blocks, reinterpret_cast<const void*>(&estep_resp_split_kernel<RR, WW, OO>), 64 * WW, 0);         \
+            &blocks,                                                                                           \
+            inline_image ? reinterpret_cast<const void*>(&estep_resp_split_inline_kernel<RR, WW, OO>)          \
+                         : reinterpret_cast<const void*>(&estep_resp_split_kernel<RR, WW, OO>),                \
+            64 * WW, 0);                                                                                       \
         *waves_per_cu = blocks * WW;                                                                           \
         return e;                                                                                              \
     }
@@ -741,11 +807,11 @@ hipError_t estep_resp_split_occupancy(int variant, int Kp, int* waves_per_cu) {
     return hipErrorInvalidValue;
 }
 
-const char* estep_resp_split_name(int variant, int Kp) {
+const char* estep_resp_split_name(int variant, int Kp, bool inline_image) {
     static thread_local char buf[64];
     int wpb, occ;
     split_cfg(Kp / 16, variant, &wpb, &occ);
-    snprintf(buf, sizeof buf, "estep_resp_split_kernel<%d,%d,%d>", Kp / 16, wpb, occ);
+    snprintf(buf, sizeof buf, "estep_resp_split%s_kernel<%d,%d,%d>", inline_image ? "_inline" : "", Kp / 16, wpb, occ);
     return buf;
 }
 

@@ -48,10 +48,12 @@ hipError_t launch_estep_resp_mfma(int variant, const float* ep, int Kp, int K, c
 hipError_t estep_resp_mfma_occupancy(int variant, int Kp, int* blocks_per_cu);
 const char* estep_resp_mfma_name(int variant, int Kp);
 bool estep_resp_split_supported(int Kp);
-hipError_t launch_estep_resp_split(int variant, const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
-                                   int64_t resident_waves, float* resp, hipStream_t st);
-hipError_t estep_resp_split_occupancy(int variant, int Kp, int* waves_per_cu);
-const char* estep_resp_split_name(int variant, int Kp);
+size_t estep_resp_image_bytes(int Kp);
+hipError_t launch_estep_resp_image(const float* ep, int Kp, void* img, hipStream_t st);
+hipError_t launch_estep_resp_split(int variant, const float* ep, const void* img, int Kp, int K, const SamplesDev& s,
+                                   int64_t n, int64_t resident_waves, float* resp, hipStream_t st);
+hipError_t estep_resp_split_occupancy(int variant, int Kp, bool inline_image, int* waves_per_cu);
+const char* estep_resp_split_name(int variant, int Kp, bool inline_image);
 hipError_t launch_estep_stats_tile(int variant, const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
                                    int64_t chunk, int blocks, float* partials, int pstride, hipStream_t st,
                                    const LeafDesc* leaves = nullptr, const int2* items = nullptr);
@@ -500,6 +502,14 @@ struct sdmm_mix {
     EmStateDev S{};
     float* ep = nullptr;
     float* gp = nullptr;
+    // the split kernel's coefficient image of ep (estep_split.hip): allocated
+    // and built by the first sdmm_responsibilities that needs it, rebuilt when
+    // ep has been written since (ep_written), never copied to a clone
+    bool rimg_inline = false;    // SDMM_RESP_IMAGE=inline: every workgroup builds its own
+    void* rimg = nullptr;
+    uint64_t ep_epoch = 1;       // bumped wherever a writer of ep is enqueued
+    uint64_t rimg_epoch = 0;     // the ep_epoch rimg was built at (0: never)
+    int64_t rimg_builds = 0;     // builder launches so far (sdmm_resp_image_builds)
     double* stats = nullptr;     // compact stats (2 + 21K)
     double* tmp_mean = nullptr;  // K*6 (set_params / init)
     double* tmp_cov = nullptr;   // K*25
@@ -599,6 +609,11 @@ int comm_broadcast(sdmm_comm* c, void* dbuf, size_t bytes, int root, hipStream_t
 }  // namespace
 
 namespace {
+
+// Called wherever a writer of m->ep is enqueued (a kernel, a copy, a
+// broadcast), before or after the enqueue: the next split-kernel
+// sdmm_responsibilities rebuilds the coefficient image behind that writer.
+inline void ep_written(sdmm_mix* m) { ++m->ep_epoch; }
 
 int choose_layout(int K, int& cpl, int& lps) {
     // components are evaluated in packed pairs: CPL is always even
@@ -909,6 +924,10 @@ int create_impl(int K, const sdmm_em_params* params, int device, hipStream_t ord
         }
         if (mfma) m->rtile = 2;
         if (split && estep_resp_split_supported(m->Kp)) m->rtile = 3;
+        // SDMM_RESP_IMAGE=inline: the split kernel whose workgroups build the
+        // coefficient image themselves (A/B runs, the bitwise tests)
+        const char* iv = std::getenv("SDMM_RESP_IMAGE");
+        m->rimg_inline = iv && std::strcmp(iv, "inline") == 0;
         // statistics: the tile kernel for 64 < K <= 128, its GROUP form for
         // 128 < K <= 512 (estep.hip), estep_stats_kernel otherwise
         if (K > 64 && K <= 128) m->stile = 1;
@@ -916,7 +935,7 @@ int create_impl(int K, const sdmm_em_params* params, int device, hipStream_t ord
     }
     static thread_local OccCache occ[8];
     OccCache& oc = occ[(K * 7 + device) & 7];
-    const int kern = ((m->rtile * 16 + m->rvariant) * 16 + m->stile) * 16 + m->svariant;
+    const int kern = (((m->rtile * 16 + m->rvariant) * 16 + m->stile) * 16 + m->svariant) * 2 + (m->rimg_inline ? 1 : 0);
     if (oc.K == K * 64 + device && oc.kern == kern) {
         m->resp_blocks = oc.resp;
         m->stats_blocks = oc.stats;
@@ -929,7 +948,7 @@ int create_impl(int K, const sdmm_em_params* params, int device, hipStream_t ord
             return cleanup(fail(SDMM_E_HIP, "E-step occupancy query failed"));
         if (m->rtile == 3) {
             int wpc = 0;
-            if (estep_resp_split_occupancy(m->rvariant, m->Kp, &wpc) != hipSuccess)
+            if (estep_resp_split_occupancy(m->rvariant, m->Kp, m->rimg_inline, &wpc) != hipSuccess)
                 return cleanup(fail(SDMM_E_HIP, "E-step occupancy query failed"));
             m->resp_blocks = wpc;   // resident waves per CU (split kernel)
         }
@@ -982,6 +1001,7 @@ int create_impl(int K, const sdmm_em_params* params, int device, hipStream_t ord
     // packed records: every component dead until init/set_params
     if (launch_pack_all(K, m->Kp, m->C, m->ep, m->gp, m->norm5, m->stream) != hipSuccess)
         return cleanup(fail(SDMM_E_HIP, "pack kernel launch failed"));
+    ep_written(m);
     if (!on_stream && hipStreamSynchronize(m->stream) != hipSuccess)
         return cleanup(fail(SDMM_E_HIP, "hipStreamSynchronize failed"));
     *out = m;
@@ -1032,6 +1052,7 @@ int create_many(int K, const sdmm_em_params* params, int device, hipStream_t st,
         constructor_scalars(m0, scal);
         e = launch_init_pack_many(n, K, m0->Kp, scal, m0->params.bprior, (float)m0->params.epsilon, m0->S.scalars,
                                   m0->S.bPriors, m0->S.bDepth, m0->C, m0->ep, m0->gp, m0->norm5, stride, st);
+        for (int i = 0; i < n; ++i) ep_written(out[i]);
     }
     if (r || e != hipSuccess) {
         // hold the slab across the members' destruction: the last member's
@@ -1070,6 +1091,7 @@ void sdmm_detail::destroy_impl(sdmm_mix* m, bool sync) {
         (void)hipFree(m->block);
     }
     if (m->partials) (void)hipFree(m->partials);
+    if (m->rimg) (void)hipFree(m->rimg);
     if (m->guide_fb) (void)hipFree(m->guide_fb);
     // after the handle's last product launch (streams are synchronised above
     // or by destroy_many)
@@ -1133,6 +1155,7 @@ int copy_prefix_many(const sdmm_mix* const* src, sdmm_mix* const* dst, int n, hi
         dst[i]->guide_cap = src[i]->guide_cap;
         dst[i]->guide_order = src[i]->guide_order;
         dst[i]->initialised = src[i]->initialised;
+        ep_written(dst[i]);
         ptrs[(size_t)i] = src[i]->C.weights;
         ptrs[(size_t)n + i] = dst[i]->C.weights;
     }
@@ -1234,12 +1257,18 @@ int sdmm_layout(const sdmm_mix* m, int* resp_cpl, int* resp_lps, int* stats_cpl,
     return SDMM_OK;
 }
 
+int sdmm_resp_image_builds(const sdmm_mix* m, int64_t* count) {
+    if (!m || !count) return fail(SDMM_E_INVALID, "invalid argument");
+    *count = m->rimg_builds;
+    return SDMM_OK;
+}
+
 const char* sdmm_kernel_name(const sdmm_mix* m, int which) {
     if (!m) return "";
     static thread_local char buf[64];
     if (which == 0) {
         if (m->rtile == 3) {
-            std::snprintf(buf, sizeof buf, "%s", estep_resp_split_name(m->rvariant, m->Kp));
+            std::snprintf(buf, sizeof buf, "%s", estep_resp_split_name(m->rvariant, m->Kp, m->rimg_inline));
             return buf;
         } else if (m->rtile == 2) {
             std::snprintf(buf, sizeof buf, "%s", estep_resp_mfma_name(m->rvariant, m->Kp));
@@ -1303,6 +1332,7 @@ static int upload_and_set(sdmm_mix* m, const float* weights, const float* means,
     HIP_TRY(hipMemcpyAsync(m->tmp_mean, md, 8 * 6 * K, hipMemcpyHostToDevice, m->stream));
     HIP_TRY(hipMemcpyAsync(m->tmp_cov, cd, 8 * 25 * K, hipMemcpyHostToDevice, m->stream));
     HIP_TRY(hipMemcpyAsync(m->C.weights, cd + 25 * K, 4 * K, hipMemcpyHostToDevice, m->stream));
+    ep_written(m);
     HIP_TRY(launch_set_all(m->K, m->Kp, m->tmp_mean, m->tmp_cov, m->C, m->ep, m->gp, m->norm5, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));  // the bounce buffer is reused by the thread's next call
     m->initialised = true;
@@ -1434,6 +1464,7 @@ static int init_hemisphere_batched_impl(sdmm_mix* const* mixes, int n, const flo
     for (int i = 0; i < n; ++i) {
         sdmm_mix* m = mixes[i];
         tab[i] = InitDescHost{m->C, m->ep, m->gp, m->S.bPriors, m->S.bDepth, m->tmp_mean, m->tmp_cov};
+        ep_written(m);
     }
     const size_t in_off = stage_bytes + tab_bytes;   // device offsets of the inputs
     const size_t dist_off = in_off + 2 * pn_bytes;
@@ -1543,6 +1574,7 @@ int sdmm_mstep(sdmm_mix* m, const double* stats, int64_t n_total) {
     if (!m || !stats) return fail(SDMM_E_INVALID, "invalid argument");
     if (!m->initialised) return fail(SDMM_E_STATE, "mixture not initialised");
     HIP_TRY(hipSetDevice(m->device));
+    ep_written(m);
     HIP_TRY(launch_mstep(m->K, m->Kp, stats, n_total, m->C, m->S, m->ep, m->gp, m->norm5, m->tmp_mean,
                          m->mcount, m->stream));
     return SDMM_OK;
@@ -1630,6 +1662,7 @@ int sdmm_em_step_sharded(sdmm_mix* m, sdmm_comm* c, const sdmm_samples* shard, i
         HIP_TRY(launch_set_f64(m->stats + len, (double)shard->n, m->stream));
         // SUM over ranks, then the same M-step everywhere (n from the summed count)
         if ((r = comm_allreduce(c, m->stats, len + 1, m->stream))) return r;
+        ep_written(m);
         HIP_TRY(launch_mstep(m->K, m->Kp, m->stats, -1, m->C, m->S, m->ep, m->gp, m->norm5, m->tmp_mean,
                              m->mcount, m->stream));
     }
@@ -1652,6 +1685,7 @@ int sdmm_mix_broadcast(sdmm_mix* const* mixes, int n_mix, const int32_t* owner, 
     // a mixture's parameters, derived arrays, packed records and stepwise state
     // are one contiguous prefix of its device block (everything before the stats)
     const size_t bytes = (size_t)((char*)mixes[0]->stats - (char*)mixes[0]->C.weights);
+    for (int i = 0; i < n_mix; ++i) ep_written(mixes[i]);
     if (c->nccl) {
         ncclResult_t g = ncclGroupStart();
         if (g != ncclSuccess) return nccl_fail(g, "ncclGroupStart");
@@ -1686,6 +1720,7 @@ int sdmm_clone(const sdmm_mix* src, sdmm_mix** out) {
     const size_t bytes = (size_t)((char*)src->stats - (char*)src->C.weights);
     hipError_t e = hipSetDevice(src->device);
     if (e == hipSuccess) e = hipMemcpyAsync(m->C.weights, src->C.weights, bytes, hipMemcpyDeviceToDevice, m->stream);
+    ep_written(m);   // (the clone has no image yet: it builds its own on first use)
     if (e != hipSuccess) {
         sdmm_destroy(m);
         return fail(SDMM_E_HIP, std::string("sdmm_clone: ") + hipGetErrorString(e));
@@ -1705,6 +1740,7 @@ int sdmm_em_step(sdmm_mix* m, const sdmm_samples* s, int iterations) {
     for (int it = 0; it < iterations; ++it) {
         r = run_estep_stats(m, s, m->stats);
         if (r) return r;
+        ep_written(m);
         HIP_TRY(launch_mstep(m->K, m->Kp, m->stats, s->n, m->C, m->S, m->ep, m->gp, m->norm5, m->tmp_mean,
                              m->mcount, m->stream));
     }
@@ -1882,6 +1918,7 @@ int batched_iteration(sdmm_mix* const* mixes, int n_mix, const sdmm_samples* s, 
         leaves[i] = LeafDesc{m->ep, lstats, s0[i], n, plans[(size_t)i].chunk, row, plans[(size_t)i].blocks};
         mixd[i] = MixDesc{m->C, m->S, m->ep, m->gp, lstats, m->tmp_mean, m->tmp_cov, cnt[i] < 0 ? 0 : n,
                           (comm && cnt[i] >= 0) ? sh + len * (size_t)n_mix + i : nullptr};
+        ep_written(m);   // (also a leaf the M-step leaves unchanged: a rebuild of the same image)
         counts[i] = (double)n;
         for (int b = 0; b < plans[(size_t)i].blocks; ++b) items[row + b] = int2{i, b};
         row += plans[(size_t)i].blocks;
@@ -2020,7 +2057,16 @@ int sdmm_responsibilities(sdmm_mix* m, const sdmm_samples* s, float* resp) {
     if (s->n == 0) return SDMM_OK;
     if (m->rtile == 3) {
         const int64_t resident = (int64_t)m->cus * (m->resp_blocks > 0 ? m->resp_blocks : 1);
-        HIP_TRY(launch_estep_resp_split(m->rvariant, m->ep, m->Kp, m->K, to_dev(s), s->n, resident, resp, m->stream));
+        if (!m->rimg_inline && m->rimg_epoch != m->ep_epoch) {
+            // the image of the current ep, behind ep's last writer on the stream
+            // and ahead of the kernel that reads it (where the in-kernel build reads ep)
+            if (!m->rimg) HIP_TRY(hipMalloc(&m->rimg, estep_resp_image_bytes(m->Kp)));
+            HIP_TRY(launch_estep_resp_image(m->ep, m->Kp, m->rimg, m->stream));
+            m->rimg_epoch = m->ep_epoch;
+            ++m->rimg_builds;
+        }
+        HIP_TRY(launch_estep_resp_split(m->rvariant, m->ep, m->rimg_inline ? nullptr : m->rimg, m->Kp, m->K, to_dev(s),
+                                        s->n, resident, resp, m->stream));
         return SDMM_OK;
     }
     if (m->rtile == 2) {
@@ -2175,6 +2221,7 @@ int sdmm_set_state(sdmm_mix* m, const double* scalars, const double* T, const do
         {(void*)sgM, m->S.sgM, 40 * K}, {(void*)sgC, m->S.sgC, 200 * K}, {(void*)bpriors, m->S.bPriors, 100 * K},
         {(void*)bdepth, m->S.bDepth, 36 * K},
     };
+    ep_written(m);   // (the stepwise state feeds the next M-step only; kept with the other setters)
     const int r = xfer(items, (int)(sizeof(items) / sizeof(items[0])), true, m->stream);
     if (r) return r;
     return SDMM_OK;
@@ -2205,6 +2252,7 @@ int sdmm_restore_params(sdmm_mix* m, const sdmm_params_out* in) {
     for (const XferItem& it : items)
         if (!it.host) return fail(SDMM_E_INVALID, "sdmm_restore_params: every array is required");
     HIP_TRY(hipSetDevice(m->device));
+    ep_written(m);
     const int r = xfer(items, (int)(sizeof(items) / sizeof(items[0])), true, st);
     if (r) return r;
     HIP_TRY(launch_pack_all(m->K, m->Kp, m->C, m->ep, m->gp, m->norm5, st));

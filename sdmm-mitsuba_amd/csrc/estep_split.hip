@@ -45,6 +45,9 @@
 // the lane's own 4 R components and then the sample's four lane groups by two
 // row swaps (v_permlane16_swap, v_permlane32_swap), and the rows go out as
 // 16-B stores (K = 128: staged through LDS into 256-B half rows).
+//
+// At R = 8 the default is the band form further down (resp_band_body): the
+// image stays in registers, a wave owning 32 components instead of 16 samples.
 #include "sdmm_device.h"
 
 namespace sdmm {
@@ -657,10 +660,25 @@ __device__ __forceinline__ void resp_split_body(const float* __restrict__ ep, co
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 f4 D[8];
+#ifdef SDMM_SPLIT_DIAG_ONEFRAG
+                // diagnostic ceiling (tools/build_variant.sh "-DSDMM_SPLIT_DIAG_ONEFRAG"):
+                // block 0's fragments and detInv pi quad, read once per tile,
+                // serve all R blocks -- 8 fragment reads per tile instead of
+                // 8 R, the same matrix and pair math; the rows are not
+                // responsibilities.  (The empty asm: the registers are opaque
+                // per block, so the R identical blocks are not folded into one.)
+#pragma unroll
+                for (int f = 0; f < 8; ++f) asm volatile("" : "+v"(F[0][f]));
+                asm volatile("" : "+v"(dp[0]));
+                forms(F[0], Bs, Bd, D);
+                __builtin_amdgcn_sched_barrier(0);
+                pair_math(r, Tag<false>{}, D, dp[0]);
+#else
                 forms(F[r & 1], Bs, Bd, D);
                 __builtin_amdgcn_sched_barrier(0);
                 pair_math(r, Tag<false>{}, D, dp[r & 1]);
                 if (r + 1 < R) frags(r + 1, F[(r + 1) & 1], dp[(r + 1) & 1]);
+#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -720,6 +738,347 @@ estep_resp_split_inline_kernel(const float* __restrict__ ep, int Kp, int K, Samp
 }
 
 // ---------------------------------------------------------------------------
+// Band form at R = 8 (round 9): the coefficient image lives in registers.
+//
+// resp_split_body re-reads the mixture's whole 64-KB image from LDS for every
+// 16-sample tile (64 ds_read_b128 per tile, 4.7 GB of LDS reads per launch at
+// N = 2^20).  Here a wave owns a band of COMPONENTS instead: wave w of a
+// 4-wave workgroup keeps blocks 2 w and 2 w + 1 (components 32 w .. 32 w + 31:
+// 16 fragments = 64 VGPRs, what the F[2][8] double buffer cost, and two
+// detInv pi quads) for the whole launch, and the four waves together cover
+// K = 128.  The work unit is a super-tile of 64 samples, four 16-sample tiles;
+// wave w is the builder and the storer of tile w:
+//
+//   1. features of its tile from its DMA ring (the counted vmcnt waits of
+//      resp_split_body), the sample fragments Bs / Bd into the workgroup's
+//      fragment buffer; the lane keeps its sample's hp, dif, dzero.  Barrier X.
+//   2. for each of the four tiles: Bs / Bd from the buffer, 16 MFMAs and two
+//      pdf_quad blocks against the resident fragments, the unnormalised pdfs
+//      straight into the workgroup's row stage ([64 rows][512 B], the wave's
+//      128-B band of each row; the rows 528 B apart, so that the eight rows of
+//      a write's lane group fall on different banks: conflict-free writes and
+//      reads with constant offsets), the lane's partial normaliser (its 8
+//      components of the sample, summed as resp_split_body's acc / acc2) into
+//      part[tile][w][lane], and a flag per tile where its band holds a rare
+//      angle or a NaN.  Barrier A.  A tile that any wave flagged is redone by
+//      all four with the reference's quirks, behind one more barrier (a few
+//      super-tiles per launch): the scope of resp_split_body's redo, all 128
+//      components of the tile's 16 samples.
+//   3. rows 16 w .. 16 w + 15: lane (g, col) reads the four waves' partials
+//      P0 .. P3 of its own place in tile w and the sample's normaliser is
+//      rows_sum4((P0 + P1) + (P2 + P3)) -- the waves first, in that fixed
+//      order, then the four lane groups by the two row swaps; the heuristic
+//      mix, v_rcp and the selects as in resp_split_body; the 16 row scales
+//      pass through 64 B of LDS into the store layout (lane L: row 2 i +
+//      (L >> 5) of store i; wave-local, no barrier), and the rows go from the
+//      stage, scaled, as 8 stores of two whole 512-B rows each.
+//
+// Barrier X of the next super-tile also frees the stage.  The unnormalised
+// pdfs are resp_split_body's bits; only the normaliser's summation order
+// differs (128 non-negative terms: at most 127 2^-24 relative).
+constexpr int kBandWaves = 4;
+constexpr int kBandRowU4 = 33;   // a stage row: 32 chunks of 16 B and one of padding
+constexpr int kBandOcc = 3;   // workgroups per CU = waves per SIMD
+
+// LDS-only workgroup barrier: the row stores in flight stay in flight (no
+// vmcnt wait; every exchange between the waves goes through LDS)
+__device__ __forceinline__ void band_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+template <bool INLINE>
+__device__ __forceinline__ void resp_band_body(const float* __restrict__ ep, const u4* __restrict__ img, int Kp, int K,
+                                               const SamplesDev& s, int64_t n, float* __restrict__ resp) {
+    constexpr int R = 8, NC = R * 8 * 64, NF = kFeatSlots * kFeatSlotU4;
+    // the carve: the four feature rings (first: LDS-DMA destinations below
+    // 64 KB), the fragment buffer (4 tiles x (Bs, Bd) x 64 lanes), the row
+    // stage (64 rows x (32 + 1 pad) chunks), the lanes' partial normalisers
+    // (4 tiles x 4 waves x 64 lanes), per wave the 16 row scales of its tile
+    constexpr int NB = 4 * 2 * 64, NST = 64 * kBandRowU4, NP = 4 * 4 * 64 / 4, NG = 4;
+    constexpr int NTOT = kBandWaves * NF + NB + NST + NP + kBandWaves * NG + 1;   // (+ the four redo flags)
+    static_assert(kBandOcc * NTOT * 16 <= 163840, "three workgroups' carved LDS blocks exceed the 160 KB of a CU");
+    static_assert(kBandWaves * NF * 16 <= 65536, "LDS-DMA destinations stay below 64 KB");
+    __shared__ u4 smem[NTOT];
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 4, col = lane & 15;
+    u4* const ring = smem + w * NF;
+    u4* const fbuf = smem + kBandWaves * NF;
+    f4* const stg = (f4*)(fbuf + NB);
+    float* const part = (float*)(stg + NST);
+    f4* const gsv = stg + NST + NP + w * NG;
+    unsigned* const flags = (unsigned*)(stg + NST + NP + kBandWaves * NG);
+
+    // the wave's band, resident: blocks 2 w and 2 w + 1
+    bf8 F[2][8];
+    f4 dp[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+#pragma unroll
+        for (int f = 0; f < 8; ++f) {
+            const int idx = ((2 * w + b) * 8 + f) * 64 + lane;
+            F[b][f] = __builtin_bit_cast(bf8, INLINE ? image_entry(ep, Kp, idx, NC) : img[idx]);
+        }
+        const int idx = NC + (2 * w + b) * 4 + g;
+        dp[b] = __builtin_bit_cast(f4, INLINE ? image_entry(ep, Kp, idx, NC) : img[idx]);
+    }
+
+    // Super-tiles dealt round robin over the launch's workgroups (one round of
+    // resident ones): workgroup b serves b, b + G, ..., so the rows written at
+    // one time are neighbouring 32-KB blocks (a contiguous range per workgroup
+    // would repeat the channel aliasing described in resp_split_body).  Every
+    // wave of the workgroup runs all nit super-tiles (the barriers); its own
+    // tile of the last one may be partial (rows_last rows) or empty.
+    const int64_t nsup = (n + 63) >> 6;
+    if ((int64_t)blockIdx.x >= nsup) return;
+    const int nit = (int)((nsup - 1 - blockIdx.x) / gridDim.x) + 1;
+    const int64_t s0 = 64 * (int64_t)blockIdx.x + 16 * w, step = 64 * (int64_t)gridDim.x, s1 = n;
+    const int64_t span = s1 - s0;
+    const uint64_t whole = (uint64_t)(span - 16);
+    const int jfull = span < 16          ? 0
+                      : (whole >> 32) == 0 ? (int)((uint32_t)whole / (uint32_t)step) + 1
+                                           : (int)(whole / (uint64_t)step) + 1;
+    const int64_t tl = s0 + jfull * step;   // the wave's first tile that is not whole
+    const int rows_last = tl < s1 ? (int)(s1 - tl) : 0;
+
+    const bool has_h = s.hpdf != nullptr, has_d = s.isDiffuse != nullptr;
+    // DMA sources of this lane, as in resp_split_body: sample sl = lane >> 2
+    // of the tile, plane pl = lane & 3 of piece 0 and of piece 1
+    const int pl = lane & 3, sl = lane >> 2;
+    const uintptr_t src0 = (uintptr_t)(pl == 0 ? s.x[0] : pl == 1 ? s.x[1] : pl == 2 ? s.x[2] : s.x[3]);
+    const bool byteplane = pl == 3 && has_d;
+    const uintptr_t src1 = (uintptr_t)(pl == 0   ? s.x[4]
+                                       : pl == 1 ? s.x[5]
+                                       : pl == 2 ? (has_h ? s.hpdf : s.x[0])
+                                                 : (has_d ? (const float*)s.isDiffuse : s.x[0]));
+    const unsigned sh1 = byteplane ? 0 : 2;
+    const unsigned ring_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) u4*)ring;
+    // The lane's two source addresses run with the wave's tiles: dma() is
+    // called for tiles 0, 1, ... in order.  A whole tile reads its own samples
+    // and advances the addresses by the step.  Tile jfull (wave-uniform: the
+    // end of the wave's run) moves them back once to its samples clamped to
+    // the last one, s1 - 1 (tail = s1 - 1 - tl lies in -64 .. 14: the tile is
+    // partial or an empty one of the last super-tile), and they stay there for
+    // the ring's look-ahead past the end (records that are never used).  No
+    // clamped address is kept in registers through the loop.
+    uintptr_t dp0 = src0 + ((uintptr_t)(s0 + sl) << 2);
+    uintptr_t dp1 = src1 + ((uintptr_t)(s0 + sl) << sh1);
+    const int tail = (int)(s1 - 1 - tl);
+    auto dma = [&](int j, int slot) __attribute__((always_inline)) {
+        if (j == jfull) {
+            int t2 = tail;
+            asm volatile("" : "+s"(t2));
+            const int back = t2 - (lane >> 2) < 0 ? t2 - (lane >> 2) : 0;
+            dp0 += (uintptr_t)((intptr_t)back << 2);
+            dp1 += (uintptr_t)((intptr_t)back << sh1);
+        }
+        dma_pair(dp0, dp1 & ~(uintptr_t)3, ring_lds + (unsigned)slot * (kFeatSlotU4 * 16u));
+        const unsigned adv = j < jfull ? (unsigned)step : 0u;
+        dp0 += adv << 2;
+        dp1 += adv << sh1;
+    };
+    // the low bits of the sample that the lane's record of the wave's last,
+    // not whole tile holds (the DMA's clamp)
+    const int64_t ilc = tl + col < s1 ? tl + col : s1 - 1;
+    const unsigned last_low = (unsigned)ilc;
+
+    auto forms = [&](const bf8 (&Fb)[8], bf8 bs, bf8 bd, f4 (&D)[8]) __attribute__((always_inline)) {
+        const f4 z = f4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int f = 0; f < 8; ++f) D[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Fb[f], f < 3 ? bd : bs, z, 0, 0, 0);
+    };
+
+    // store phase constants: store i writes rows 2 i and 2 i + 1 of the wave's
+    // tile, lane L the 16-B chunk L & 31 of row 2 i + (L >> 5)
+    const int hi = lane >> 5, ch = lane & 31;
+
+#pragma unroll
+    for (int a = 0; a < kFeatAhead; ++a) dma(a, a);
+    unsigned hist = 0;   // bit j: the store phase j + 1 super-tiles back was full (exactly R stores)
+    unsigned tlow = (unsigned)s0;
+    char* rowt = (char*)(resp + s0 * (int64_t)K);
+    const int64_t rowstep = step * (int64_t)K * 4;
+    for (int it = 0; it < nit; ++it, tlow += (unsigned)step) {
+        // -- 1: the wave's own tile: features, fragments
+        const int slot = it % kFeatSlots;
+        dma(it + kFeatAhead, (it + kFeatAhead) % kFeatSlots);
+        // younger than this tile's DMA: the pieces of the two tiles after it
+        // and the store phases of the last k = min(it, kFeatAhead) super-tiles
+        const int k = it < kFeatAhead ? it : kFeatAhead;
+        const unsigned need = (1u << k) - 1u;
+        f4 fa, fb;
+        read_feat_counted<R>(k, (hist & need) == need, ring_lds + (unsigned)slot * (kFeatSlotU4 * 16u) + 16u * col,
+                             fa, fb);
+        const float P3[3] = {fa.x - kOrigin, fa.y - kOrigin, fa.z - kOrigin};
+        const float D3[3] = {fa.w, fb.x, fb.y};
+        const bool dzero = D3[0] == 0.0f && D3[1] == 0.0f && D3[2] == 0.0f;
+        const int rows = it < jfull ? 16 : rows_last;
+        const unsigned slow = it < jfull ? tlow + (unsigned)col : last_low;
+        const unsigned fsh = (((unsigned)(uintptr_t)s.isDiffuse + slow) & 3u) << 3;
+        const bool dif = has_d && ((fbits(fb.w) >> fsh) & 0xffu) != 0u;
+        const float hp = has_h ? fb.z : 0.0f;
+        fbuf[(2 * w + 0) * 64 + lane] = __builtin_bit_cast(u4, a_frag(P3, g, true));
+        fbuf[(2 * w + 1) * 64 + lane] = __builtin_bit_cast(u4, a_frag(D3, g, false));
+        band_barrier();   // X: the four tiles' fragments are up; the stage and the partials are free
+
+        // -- 2: the wave's band of all four tiles
+        unsigned oddmask = 0;   // bit t: a rare angle or a NaN in the wave's band of tile t
+        auto tile = [&](auto rare, int t, bf8 bs, bf8 bd, u4& bsn, u4& bdn) __attribute__((always_inline)) {
+            constexpr bool RARE = decltype(rare)::value;
+            uint32_t cbits = 0;
+            f2 acc = f2{0.0f, 0.0f}, acc2 = f2{0.0f, 0.0f};
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                f4 D[8];
+                forms(F[b], bs, bd, D);
+                __builtin_amdgcn_sched_barrier(0);
+                if (!RARE && b == 1 && t < 3) {
+                    // tile t + 1's fragments are read behind tile t's last
+                    // MFMAs, under its second block's pair math
+                    bsn = fbuf[(2 * t + 2) * 64 + lane];
+                    bdn = fbuf[(2 * t + 3) * 64 + lane];
+                }
+                if constexpr (!RARE)
+                    cbits = __builtin_elementwise_max(
+                        cbits, __builtin_elementwise_max(__builtin_elementwise_max(fbits(D[0][0]), fbits(D[0][1])),
+                                                         __builtin_elementwise_max(fbits(D[0][2]), fbits(D[0][3]))));
+                f2 p[2];
+                pdf_quad<RARE>(D[0], D[1], D[2], D[3], D[4], D[5], D[6], D[7], dp[b], p);
+                stg[(16 * t + col) * kBandRowU4 + (8 * w + 4 * b + g)] = f4{p[0].x, p[0].y, p[1].x, p[1].y};
+                acc = padd(acc, p[0]);
+                acc2 = padd(acc2, p[1]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            const float ls = (acc.x + acc.y) + (acc2.x + acc2.y);
+            part[(4 * t + w) * 64 + lane] = ls;
+            if constexpr (!RARE) {
+                // a rare angle (c < -0.9999995; its bits, unsigned, exceed
+                // those of -0.9999995f) or a NaN in the wave's band of the tile
+                const bool odd = cbits > __builtin_bit_cast(uint32_t, -0.9999995f) || !(ls >= 0.0f);
+                if (__builtin_amdgcn_ballot_w64(odd) != 0) oddmask |= 1u << t;
+            }
+        };
+        {
+            u4 bsn = fbuf[lane], bdn = fbuf[64 + lane];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                tile(Tag<false>{}, t, __builtin_bit_cast(bf8, bsn), __builtin_bit_cast(bf8, bdn), bsn, bdn);
+        }
+        flags[w] = oddmask;
+        band_barrier();   // A: all bands of the stage, all partials and the four waves' flags are up
+
+        // -- 3: the wave's own tile: normalise, store
+        // (the tile's staged rows are read first: they return under the
+        // flags' round trip and the normaliser's chain)
+        const f4* const srow = stg + (16 * w) * kBandRowU4;
+        const float* const pw = part + (4 * w) * 64 + lane;
+        f4 v[8];
+        float W0, W1, W2, W3;
+        auto staged = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = srow[(2 * i + hi) * kBandRowU4 + ch];
+            W0 = pw[0], W1 = pw[64], W2 = pw[128], W3 = pw[192];
+        };
+        const u4 fl = *(const u4*)flags;
+        staged();
+        // A tile that any wave flagged is redone by every wave with the
+        // reference's quirks -- all 128 components of its 16 samples, the scope
+        // of resp_split_body's redo -- behind a barrier of its own
+        // (workgroup-uniform: every wave reads the same four flags; a few
+        // super-tiles per launch).
+        const unsigned un = (unsigned)__builtin_amdgcn_readfirstlane((int)((fl.x | fl.y) | (fl.z | fl.w)));
+        if (un != 0) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (un & (1u << t)) {
+                    u4 d0, d1;
+                    tile(Tag<true>{}, t, __builtin_bit_cast(bf8, fbuf[(2 * t) * 64 + lane]),
+                         __builtin_bit_cast(bf8, fbuf[(2 * t + 1) * 64 + lane]), d0, d1);
+                }
+            band_barrier();
+            staged();
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const float S = rows_sum4((W0 + W1) + (W2 + W3));
+        const float S2 = dif ? fmaf(1.0f - kHeuristicWeight, S, kHeuristicWeight * hp) : S;
+        const float inv = __builtin_amdgcn_rcpf(S2);
+        const bool fin = __builtin_isfinite(inv) && !dzero;
+        const float gsc = fin ? (dif ? inv * (1.0f - kHeuristicWeight) : inv) : 0.0f;
+        // a non-finite sum means a non-finite pdf (NaN/inf input): zero rows by select
+        const bool bad = __builtin_amdgcn_ballot_w64(!__builtin_isfinite(S)) != 0;
+        const bool full = rows == 16 && (16 * R == K) && !bad;
+        // the row scales in store order: row r at (r & 1) * 8 + (r >> 1), so
+        // the lane's eight rows 2 i + hi are two 16-B reads (the wave's own
+        // LDS accesses run in order: no barrier)
+        ((float*)gsv)[(col & 1) * 8 + (col >> 1)] = gsc;
+        const f4 sa = gsv[2 * hi], sb = gsv[2 * hi + 1];
+        const float scl[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
+        __builtin_amdgcn_sched_barrier(0);
+        if (full) {
+            // (the empty asm statements: the offset is formed here, from the
+            // lane index, and not kept in a register through the loop)
+            unsigned vo = (unsigned)lane;
+            asm volatile("" : "+v"(vo));
+            vo *= 16u;
+            unsigned up = 4 * 2 * (16 * R) * 4;
+            asm volatile("" : "+s"(up));
+            char* const upper = rowt + up;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const f2 sc = spl(scl[i]);
+                const f2 lo = f2{v[i].x, v[i].y} * sc, hh = f2{v[i].z, v[i].w} * sc;
+                __builtin_nontemporal_store(f4{lo.x, lo.y, hh.x, hh.y},
+                                            (f4*)((i < 4 ? rowt : upper) + vo + (i & 3) * (2 * (16 * R) * 4)));
+            }
+        } else if (rows > 0) {
+            // (the opaque K: the element offsets are worked out here, not
+            // hoisted out of the loop into 32 more VGPR pairs)
+            int Ko = K;
+            asm volatile("" : "+s"(Ko));
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int rw = 2 * i + hi;
+                const float sc = scl[i];
+                if (rw < rows) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float o = sc != 0.0f ? v[i][j] * sc : 0.0f;
+                        if (4 * ch + j < Ko)
+                            __builtin_nontemporal_store(o, (float*)(rowt + ((unsigned)(rw * Ko + 4 * ch + j) << 2)));
+                    }
+                }
+            }
+        }
+        hist = (hist << 1) | (full ? 1u : 0u);
+        rowt += rowstep;
+    }
+    // the ring's last DMAs (clamped tiles past the end) land before the
+    // workgroup's LDS is released
+    wait_vm<0>();
+}
+
+// (the template arguments name the configuration like estep_resp_split_kernel's:
+// R blocks, waves per workgroup, workgroups' waves per SIMD)
+template <int R, int WPB, int OCC>
+__global__ void __launch_bounds__(64 * WPB, OCC)
+estep_resp_split_band_kernel(const float* __restrict__ ep, const u4* __restrict__ img, int Kp, int K, SamplesDev s,
+                             int64_t n, float* __restrict__ resp) {
+    static_assert(R == 8 && WPB == kBandWaves, "the band form is four waves over K = 128");
+    resp_band_body<false>(ep, img, Kp, K, s, n, resp);
+}
+
+// SDMM_RESP_IMAGE=inline: the band's fragments built from ep in the prologue
+template <int R, int WPB, int OCC>
+__global__ void __launch_bounds__(64 * WPB, OCC)
+estep_resp_split_band_inline_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev s, int64_t n,
+                                    float* __restrict__ resp) {
+    static_assert(R == 8 && WPB == kBandWaves, "the band form is four waves over K = 128");
+    resp_band_body<true>(ep, nullptr, Kp, K, s, n, resp);
+}
+
+// ---------------------------------------------------------------------------
 // Configurations (R = Kp / 16 blocks, waves per workgroup, waves per SIMD).
 // The B image takes R x 8 KB of LDS per workgroup.
 #ifndef SDMM_SPLIT_R8_WPB   // (overridable for tools/build_variant.sh A/B builds)
@@ -728,17 +1087,25 @@ estep_resp_split_inline_kernel(const float* __restrict__ ep, int Kp, int K, Samp
 #endif
 #define SDMM_SPLIT_CONFIGS(X) X(1, 4, 4) X(2, 4, 4) X(4, 4, 4) X(8, SDMM_SPLIT_R8_WPB, SDMM_SPLIT_R8_OCC)
 
-// R = 8 (K = 128): one 12-wave workgroup per CU at 3 waves per SIMD (the
-// 64-KB coefficient image, the 48 KB of half-row stages and the 18 KB of
+// R = 8 (K = 128): the band form (resp_band_body: 4-wave workgroups, three per
+// CU, the coefficient image in registers) unless the variant asks for the LDS
+// image (kSplitLdsVariant, SDMM_RESP_KERNEL=splitlds: the A/B and comparison
+// configuration), which is one 12-wave workgroup per CU at 3 waves per SIMD
+// (the 64-KB coefficient image, the 48 KB of half-row stages and the 18 KB of
 // feature rings share the LDS).  Round 4 measured 4-wave / 2-per-SIMD and
-// 8-wave / 2-per-SIMD workgroups slower; the variant
-// argument is kept for the ABI's A/B hook and ignored.
-static void split_cfg(int R, int /*variant*/, int* wpb, int* occ) {
+// 8-wave / 2-per-SIMD workgroups of that form slower.
+constexpr int kSplitLdsVariant = 15;
+static bool split_band(int R, int variant) { return R == 8 && variant != kSplitLdsVariant; }
+static void split_cfg(int R, int variant, int* wpb, int* occ) {
     *wpb = 4;
     *occ = 4;
     if (R == 8) {
         *wpb = SDMM_SPLIT_R8_WPB;
         *occ = SDMM_SPLIT_R8_OCC;
+    }
+    if (split_band(R, variant)) {
+        *wpb = kBandWaves;
+        *occ = kBandOcc;
     }
 }
 
@@ -771,6 +1138,18 @@ hipError_t launch_estep_resp_split(int variant, const float* ep, const void* img
     const int64_t waves = blocks * wpb;
     // the kernel steps its addresses by 16 waves samples held in 32 bits
     if (waves >= (int64_t)1 << 26) return hipErrorInvalidValue;
+    if (split_band(R, variant)) {
+        // one round of resident workgroups, fewer when n has fewer super-tiles
+        const int64_t sup = (n + 63) / 64, res = resident_waves / kBandWaves > 0 ? resident_waves / kBandWaves : 1;
+        const unsigned grid = (unsigned)(sup < res ? sup : res);
+        if (img)
+            hipLaunchKernelGGL((estep_resp_split_band_kernel<8, kBandWaves, kBandOcc>), dim3(grid), dim3(64 * kBandWaves), 0, st, ep,
+                               (const u4*)img, Kp, K, s, n, resp);
+        else
+            hipLaunchKernelGGL((estep_resp_split_band_inline_kernel<8, kBandWaves, kBandOcc>), dim3(grid), dim3(64 * kBandWaves), 0, st, ep, Kp, K,
+                               s, n, resp);
+        return hipGetLastError();
+    }
 #define X(RR, WW, OO)                                                                                          \
     if (R == RR && wpb == WW && occ == OO) {                                                                   \
         if (img)                                                                                               \
@@ -792,6 +1171,15 @@ hipError_t estep_resp_split_occupancy(int variant, int Kp, bool inline_image, in
     int wpb, occ;
     split_cfg(R, variant, &wpb, &occ);
     int blocks = 0;
+    if (split_band(R, variant)) {
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &blocks,
+            inline_image ? reinterpret_cast<const void*>(&estep_resp_split_band_inline_kernel<8, kBandWaves, kBandOcc>)
+                         : reinterpret_cast<const void*>(&estep_resp_split_band_kernel<8, kBandWaves, kBandOcc>),
+            64 * kBandWaves, 0);
+        *waves_per_cu = blocks * kBandWaves;
+        return e;
+    }
 #define X(RR, WW, OO)                                                                                          \
     if (R == RR && wpb == WW && occ == OO) {                                                                   \
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(                                           \
@@ -811,7 +1199,8 @@ const char* estep_resp_split_name(int variant, int Kp, bool inline_image) {
     static thread_local char buf[64];
     int wpb, occ;
     split_cfg(Kp / 16, variant, &wpb, &occ);
-    snprintf(buf, sizeof buf, "estep_resp_split%s_kernel<%d,%d,%d>", inline_image ? "_inline" : "", Kp / 16, wpb, occ);
+    snprintf(buf, sizeof buf, "estep_resp_split%s%s_kernel<%d,%d,%d>", split_band(Kp / 16, variant) ? "_band" : "",
+             inline_image ? "_inline" : "", Kp / 16, wpb, occ);
     return buf;
 }
 

@@ -909,13 +909,16 @@ int create_impl(int K, const sdmm_em_params* params, int device, hipStream_t ord
     // 204 us per 2^20 samples).  SDMM_RESP_KERNEL selects
     // the others for A/B measurements: tile (estep_resp_tile_kernel, the VALU
     // form), mfma (f32 matrix cores, estep_mfma.hip), legacy
-    // (estep_resp_kernel<4,32>); split also for other K with Kp / 16 in {1, 2, 4}.
+    // (estep_resp_kernel<4,32>); split also for other K with Kp / 16 in {1, 2, 4};
+    // splitlds the split kernel with the coefficient image in LDS at Kp = 128
+    // (the default there keeps it in registers: estep_resp_split_band_kernel).
     {
         const char* ev = std::getenv("SDMM_RESP_KERNEL");
         const bool legacy = ev && std::strcmp(ev, "legacy") == 0;
         const bool mfma = ev && std::strcmp(ev, "mfma") == 0;
         const bool tile = ev && std::strcmp(ev, "tile") == 0;
-        const bool split = ev && std::strcmp(ev, "split") == 0;
+        const bool splitlds = ev && std::strcmp(ev, "splitlds") == 0;
+        const bool split = splitlds || (ev && std::strcmp(ev, "split") == 0);
         if (K > 64 && K <= 128 && !legacy && !mfma) {
             m->rtile = 1;
             m->rcpl = 2;
@@ -924,6 +927,7 @@ int create_impl(int K, const sdmm_em_params* params, int device, hipStream_t ord
         }
         if (mfma) m->rtile = 2;
         if (split && estep_resp_split_supported(m->Kp)) m->rtile = 3;
+        if (splitlds && m->rtile == 3) m->rvariant = 15;   // estep_split.hip kSplitLdsVariant
         // SDMM_RESP_IMAGE=inline: the split kernel whose workgroups build the
         // coefficient image themselves (A/B runs, the bitwise tests)
         const char* iv = std::getenv("SDMM_RESP_IMAGE");

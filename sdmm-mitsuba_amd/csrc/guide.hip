@@ -287,14 +287,18 @@ __device__ __forceinline__ QueryOut finish_query(const float* gp, int Kp, const 
     };
     float dir[3];
     if (!dir_in) {
-        // sampleDiscreteCdf: lower_bound == first slot with cdf >= u, else tie walk
+        // sampleDiscreteCdf: lower_bound == first slot with !(cdf < u), else tie
+        // walk.  Written as the negated `<` of the binary search: a NaN cdf (a
+        // non-finite query: every kept weight NaN) fails each of its
+        // comparisons, so lower_bound answers slot 0 -- `cdf >= u` never held
+        // there and the tie walk took the LAST slot instead
         float cdf = 0.0f, prev = 0.0f;
         int slot = -1, runStart = 0;
         for (int i = 0; i < lastIdx; ++i) {
             cdf += slot_w(i);
             if (i == 0 || cdf != prev) runStart = i;
             prev = cdf;
-            if (cdf >= u[0]) { slot = i; break; }
+            if (!(cdf < u[0])) { slot = i; break; }
         }
         if (slot < 0) slot = runStart;
         const int ksel = S.comp(slot);
@@ -1108,7 +1112,7 @@ __device__ QueryOut finish_query_wave(const float* gp, int Kp, const float c[3],
     if (lastIdx == 0 || sum2 == 0.0f) return o;   // createCdf(true) fails: BSDF only
     float dir[3];
     if constexpr (!PDF_ONLY) {
-        // sampleDiscreteCdf: lower_bound == first slot with cdf >= u, else the tie walk
+        // sampleDiscreteCdf: lower_bound == first slot with !(cdf < u) (finish_query), else the tie walk
         float cdf = 0.0f, prev = 0.0f;
         int slot = -1, runStart = 0;
         for (int base = 0; base < lastIdx && slot < 0; base += 64) {
@@ -1127,7 +1131,7 @@ __device__ QueryOut finish_query_wave(const float* gp, int Kp, const float c[3],
                     cdf += e4[e];
                     if (base + l == 0 || cdf != prev) runStart = base + l;
                     prev = cdf;
-                    if (cdf >= u[0]) { slot = base + l; break; }
+                    if (!(cdf < u[0])) { slot = base + l; break; }
                 }
             }
         }
@@ -1369,7 +1373,7 @@ __device__ __forceinline__ bool serve_full_group(const float* gp, int Kp, int K,
         for (int i = 0; i < S; ++i) f[i] = by_sum2(f[i]);
         float dir[3];
         if (!pdf_q) {
-            // sampleDiscreteCdf: lower_bound == first slot with cdf >= u, else the tie walk
+            // sampleDiscreteCdf: lower_bound == first slot with !(cdf < u) (finish_query), else the tie walk
             const float u0 = io.u0[q], u1 = io.u1[q], u2 = io.u2[q];
             float cdf = 0.0f, prev = 0.0f;
             int slot = -1, runStart = 0;
@@ -1387,7 +1391,7 @@ __device__ __forceinline__ bool serve_full_group(const float* gp, int Kp, int K,
                         cdf += b;
                         if (p == 0 || cdf != prev) runStart = p;
                         prev = cdf;
-                        if (cdf >= u0) slot = p;
+                        if (!(cdf < u0)) slot = p;
                     }
                 }
             }
@@ -1572,7 +1576,7 @@ __device__ __forceinline__ bool serve_full_group_g(const float* gp, int Kp, int 
         auto f = [&](int i) { return by_sum2(fs(i)); };
         float dir[3];
         if (!pdf_q) {
-            // sampleDiscreteCdf: lower_bound == first slot with cdf >= u, else the tie walk
+            // sampleDiscreteCdf: lower_bound == first slot with !(cdf < u) (finish_query), else the tie walk
             const float u0 = io.u0[q], u1 = io.u1[q], u2 = io.u2[q];
             float cdf = 0.0f, prev = 0.0f;
             int slot = -1, runStart = 0;
@@ -1591,7 +1595,7 @@ __device__ __forceinline__ bool serve_full_group_g(const float* gp, int Kp, int 
                         cdf += b;
                         if (p == 0 || cdf != prev) runStart = p;
                         prev = cdf;
-                        if (cdf >= u0) slot = p;
+                        if (!(cdf < u0)) slot = p;
                     }
                 }
             }

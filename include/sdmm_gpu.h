@@ -212,7 +212,8 @@ int sdmm_em_step_batched_host_iters(sdmm_mix* const* mixes, int n_mix, const sdm
  *                     sdmm_stats_len(K) doubles, into `stats` (device);
  *   (caller all-reduces `stats` with a SUM over ranks, e.g. ncclAllReduce)
  *   sdmm_mstep        consumes the global statistics; n_total = global sample
- *                     count (samples.size() of the reference).              */
+ *                     count (samples.size() of the reference), >= 0
+ *                     (SDMM_E_INVALID otherwise).                           */
 size_t sdmm_stats_len(int K);
 int sdmm_estep_stats(sdmm_mix* m, const sdmm_samples* device_samples, double* stats);
 int sdmm_mstep(sdmm_mix* m, const double* stats, int64_t n_total);

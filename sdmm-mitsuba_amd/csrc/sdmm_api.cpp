@@ -1576,6 +1576,9 @@ int sdmm_estep_stats(sdmm_mix* m, const sdmm_samples* s, double* stats) {
 
 int sdmm_mstep(sdmm_mix* m, const double* stats, int64_t n_total) {
     if (!m || !stats) return fail(SDMM_E_INVALID, "invalid argument");
+    // n_total < 0 tells the kernel to read the count from stats[sdmm_stats_len(K)],
+    // which only the sharded path's own, longer buffer holds
+    if (n_total < 0) return fail(SDMM_E_INVALID, "n_total must not be negative");
     if (!m->initialised) return fail(SDMM_E_STATE, "mixture not initialised");
     HIP_TRY(hipSetDevice(m->device));
     ep_written(m);

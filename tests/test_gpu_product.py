@@ -39,7 +39,11 @@ def _model(pkg, oracle, synth, K, iters, N=8192):
                                                 (512, 2, 8, 8, 64, 2000), (512, 2, 8, 8, 40, 2000),
                                                 # candidate capacity 0: every query through the
                                                 # full-K fallback kernel of the product path
-                                                (128, 4, 2, 6, 0, 1500), (512, 2, 8, 8, 0, 1000)])
+                                                (128, 4, 2, 6, 0, 1500), (512, 2, 8, 8, 0, 1000),
+                                                # the boundaries between the candidate list's sizes
+                                                # (16, 24, 40, 64) and the 24-entry list itself
+                                                (128, 4, 2, 6, 17, 1500), (128, 4, 2, 6, 24, 1500),
+                                                (128, 4, 2, 6, 25, 1500), (128, 4, 2, 6, 41, 1500)])
 def test_product_matches_oracle(pkg, oracle, synth, gpu, plog, K, iters, B, M, cap, nq):
     import torch
     b, mix, om = _model(pkg, oracle, synth, K, iters)
@@ -57,6 +61,12 @@ def test_product_matches_oracle(pkg, oracle, synth, gpu, plog, K, iters, B, M, c
     table = pkg.BsdfTable(bw, bmean, bcov, device=gpu)
     d, pdf, comp, h = mix.guide_product(ct, ut, table, matt, Ft)
     torch.cuda.synchronize()
+    if cap > 0:
+        # the candidate kernel of this capacity served at least one query itself
+        # (enough to show that its instance ran, not how many took that path)
+        fb = mix.guide_fallback_count()
+        plog(f"product_fallbacks_K{K}_cap{cap}", fb, nq - 1)
+        assert fb < nq
     dg = np.stack([x.cpu().numpy() for x in d], 1)
     pg, cg, hg = pdf.cpu().numpy(), comp.cpu().numpy(), h.cpu().numpy()
     dr, pr, cr, hr = oracle.guide_product_batch(om, c.T, u.T, mat, F, bw, bmean, bcov)

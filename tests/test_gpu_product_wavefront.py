@@ -13,7 +13,8 @@ within 1e-6 abs / 1e-5 rel and plain-conditional ones within 1e-5 / 1e-4 rel
 BSDF only.  Also: the mixed bounce (choice + dgiven, a pdf query where
 choice <= h) against the oracle's mixed mode, diffuse materials (the plugin's
 slice-0 rule), K = 16 and the Kitchen's K = 512 x 8 materials x 8 lobes, at
-candidate capacity 40 and 0 (every query through the full-K wave kernel)."""
+candidate capacity 40 and 0 (every query through the full-K wave kernel);
+K = 128 at capacities 24 and 41, the candidate list sizes' boundaries."""
 import numpy as np
 import pytest
 
@@ -42,7 +43,10 @@ def _check(plog, tag, hg, hr, cg, cr, dg, dr, pg, pr):
 
 @pytest.mark.parametrize("K,B,M,cap,nq", [(16, 4, 3, 40, 1 << 14), (16, 4, 3, 0, 3000),
                                           (512, 8, 8, 64, 2000), (512, 8, 8, 40, 2000),
-                                          (512, 8, 8, 0, 1000)])
+                                          (512, 8, 8, 0, 1000),
+                                          # the 24-entry candidate list, and the first capacity
+                                          # that needs the 64-entry one
+                                          (128, 2, 6, 24, 1500), (128, 2, 6, 41, 1500)])
 def test_product_wavefront_matches_oracle(pkg, oracle, synth, gpu, plog, K, B, M, cap, nq):
     import torch
     b, t, mixes, leaves = _tree_and_leaf_mixtures(pkg, synth, K, iters=2 if K <= 64 else 1)

@@ -583,7 +583,8 @@ int sdmm_stree_set_nodes(sdmm_stree* t, int n, const float* aabb, const int32_t*
 /* ---- Guided path tracing on the device (SDMMRenderer::Li) ----------------
  * An analytic scene of parallelograms (Mitsuba rectangles; a cube is six) and
  * an optional triangle mesh (sdmm_scene_desc's mesh fields; face normals) with
- * diffuse BSDFs and one-sided area emitters, rendered by a wavefront path
+ * diffuse BSDFs, one-sided area emitters and an optional environment emitter
+ * (a constant or a lat-long map: sdmm_scene_desc's env fields), rendered by a wavefront path
  * tracer whose every bounce goes through sdmm_guide_pdf_wavefront -- the
  * plugin's per-bounce sampleSurface / pdfSurface (sdmm_proc.cpp:275-590,
  * :592-871) on the device.  The Cornell Box of the test suite
@@ -833,6 +834,42 @@ typedef struct {
     const int32_t* tri_bsdf;
     const int32_t* tri_emitter;
     const int32_t* tri_flip_normals;
+    /* An environment emitter (appended after tri_flip_normals; the
+     * zero-initialise rule below covers older callers: env_kind = 0, no
+     * environment, the other env fields are then not read and everything
+     * behaves as before).  A ray that leaves the scene -- the camera ray or
+     * any bounce ray, delta lobes and rays leaving a dielectric included --
+     * returns throughput * evalEnvironment(ray) (sdmm_proc.cpp:659-671,
+     * :1047-1051) and ends the path.
+     *   env_kind            0 none; 1 constant (emitters/constant.cpp:
+     *                       env_radiance, whatever the direction); 2 a
+     *                       lat-long map (emitters/envmap.cpp:380-393, :409)
+     *   env_radiance        kind 1: returned as is (no scale, no transform)
+     *   env_width, env_height, env_pixels
+     *                       kind 2: host array [height][width][3], linear RGB;
+     *                       row 0 is the +y pole of the emitter's local frame
+     *                       (v = 0 where acos(v.y) = 0), u = atan2(v.x, -v.z)
+     *                       / 2 pi wraps horizontally, v clamps
+     *   env_scale           kind 2: m_scale, multiplies the lookup
+     *   env_world_to_local  kind 2: the linear part of toWorld.inverse(), row
+     *                       major, applied to the ray direction as given (no
+     *                       renormalisation)
+     * Every ray takes the bilinear lookup of the finest level (MIPMap::
+     * evalBilinear, render/mipmap.h:575-596): there are no ray differentials
+     * here, so not the EWA-filtered lookup Mitsuba gives its camera rays
+     * (envmap.cpp:394-407).  A direction whose texture coordinates are not
+     * finite returns 0.  The scene AABB and sdmm_scene_normalization do not
+     * change (an environment has no extent), nor does the rule for what
+     * geometry a scene must hold.
+     * SDMM_E_INVALID (with a message): a kind outside 0..2; kind 2 with a NULL
+     * map, a width or height < 1 or more than 2^26 texels; a non-finite or
+     * negative radiance, texel or scale; a non-finite matrix entry. */
+    int env_kind;
+    float env_radiance[3];
+    int env_width, env_height;
+    const float* env_pixels;
+    float env_scale;
+    float env_world_to_local[9];
 } sdmm_scene_desc;
 /* The descriptor has grown across ABI revisions (bsdf_params was appended):
  * zero-initialise it (`sdmm_scene_desc d = {0};` / `memset`) before filling
@@ -918,6 +955,16 @@ int sdmm_scene_intersect(const sdmm_scene* s, int64_t nq, const float* const o[3
  * it with the same traversal source. */
 int sdmm_scene_intersect_host(const sdmm_scene_desc* desc, int64_t nq, const float* o, const float* d, float mint,
                               float maxt, int mode, int32_t* prim, float* t);
+/* evalEnvironment of the scene's environment emitter (sdmm_scene_desc's env
+ * fields) for nq directions: d, rgb three device planes each (the direction
+ * is used as given; rgb: the radiance, 0 for a scene without an environment).
+ * Asynchronous on hip_stream.  The Li kernels run the same lookup where a ray
+ * leaves the scene. */
+int sdmm_env_eval(const sdmm_scene* s, int64_t nq, const float* const d[3], float* const rgb[3], void* hip_stream);
+/* The same entirely on the host (no HIP call: runs without a GPU) from a
+ * description -- d, rgb host arrays [nq][3]; only the env fields are read,
+ * and validated as sdmm_scene_create validates them.  Bitwise the device's. */
+int sdmm_env_eval_host(const sdmm_scene_desc* desc, int64_t nq, const float* d, float* rgb);
 /* Debug view of the BVH built for desc's mesh (host only).  max_levels: the
  * cap on inner levels (0: the traversal stack's 24; a smaller cap forces
  * median splits, and SDMM_E_INVALID when even those do not fit).  *n_nodes,

@@ -175,6 +175,8 @@ def lib():
                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdmm_scene_intersect_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                                 C.c_int, C.c_void_p, C.c_void_p]
+        L.sdmm_env_eval.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sdmm_env_eval_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.sdmm_mesh_bvh_dump.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
         L.sdmm_li_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -279,6 +281,7 @@ EXPORTED_SYMBOLS = [
     "sdmm_learned_load_json", "sdmm_bsdf_phong_host",
     "sdmm_bsdf_roughdielectric_host", "sdmm_bsdf_roughdielectric_device",
     "sdmm_scene_intersect", "sdmm_scene_intersect_host", "sdmm_mesh_bvh_dump",
+    "sdmm_env_eval", "sdmm_env_eval_host",
 ]
 
 
@@ -1254,7 +1257,10 @@ class _SceneDesc(C.Structure):
                 ("bsdf_params", C.c_void_p), ("learned_models", C.c_void_p), ("learned_models_nd", C.c_void_p),
                 ("n_mesh_vertices", C.c_int), ("mesh_vertices", C.c_void_p), ("n_triangles", C.c_int),
                 ("triangles", C.c_void_p), ("tri_bsdf", C.c_void_p), ("tri_emitter", C.c_void_p),
-                ("tri_flip_normals", C.c_void_p)]
+                ("tri_flip_normals", C.c_void_p),
+                ("env_kind", C.c_int), ("env_radiance", C.c_float * 3), ("env_width", C.c_int),
+                ("env_height", C.c_int), ("env_pixels", C.c_void_p), ("env_scale", C.c_float),
+                ("env_world_to_local", C.c_float * 9)]
 
 
 def _fill_geometry(d, desc, keep):
@@ -1286,6 +1292,43 @@ def _fill_geometry(d, desc, keep):
     for key in ("tri_bsdf", "tri_emitter", "tri_flip_normals"):
         if desc.get(key) is not None:
             setattr(d, key, arr(key, np.int32).ctypes.data)
+    _fill_env(d, desc, keep)
+
+
+def _fill_env(d, desc, keep):
+    """The environment emitter's fields of a _SceneDesc from a description
+    dict: env_kind (0 none, 1 constant, 2 lat-long map), env_radiance (kind
+    1), env_pixels [height, width, 3] (kind 2; width and height are its
+    shape), env_scale (default 1) and env_world_to_local (3x3, default the
+    identity)."""
+    d.env_kind = int(desc.get("env_kind", 0))
+    if desc.get("env_radiance") is not None:
+        for i, v in enumerate(np.asarray(desc["env_radiance"], np.float32).reshape(3)):
+            d.env_radiance[i] = float(v)
+    if desc.get("env_pixels") is not None:
+        px = np.ascontiguousarray(desc["env_pixels"], np.float32)
+        if px.ndim != 3 or px.shape[2] != 3:
+            raise SDMMError("env_pixels: an array [height, width, 3]")
+        keep["env_pixels"] = px
+        d.env_height, d.env_width = int(px.shape[0]), int(px.shape[1])
+        d.env_pixels = px.ctypes.data
+    d.env_scale = float(desc.get("env_scale", 1.0))
+    m = desc.get("env_world_to_local")
+    for i, v in enumerate(np.eye(3, dtype=np.float32).reshape(-1) if m is None else np.asarray(m, np.float32).reshape(9)):
+        d.env_world_to_local[i] = float(v)
+
+
+def env_eval_host(desc, d):
+    """sdmm_env_eval_host: the environment emitter's radiance for directions d
+    (numpy [nq, 3], used as given) entirely on the host (no GPU) from a
+    description's env fields (the other fields are not read) -> float32 [nq,
+    3]; 0 without an environment."""
+    sd, keep = _SceneDesc(), {}
+    _fill_env(sd, desc, keep)
+    dd = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    rgb = np.empty((len(dd), 3), np.float32)
+    _check(lib().sdmm_env_eval_host(C.byref(sd), len(dd), dd.ctypes.data, rgb.ctypes.data))
+    return rgb
 
 
 def intersect_host(desc, o, d, mint=1e-4, maxt=float("inf"), mode=0):
@@ -1752,6 +1795,24 @@ class Scene:
                                           float(mint), float(maxt), int(mode), prim.data_ptr(), t.data_ptr(),
                                           C.c_void_p(int(s_.cuda_stream) or None)))
         return prim, t
+
+    def env_eval(self, d, stream=None):
+        """sdmm_env_eval: the environment emitter's radiance for directions on
+        device planes -- d: 3 float32 device tensors of nq each -> 3 float32
+        device tensors (r, g, b); 0 for a scene without an environment;
+        bitwise env_eval_host's."""
+        import torch
+        nq = d[0].numel()
+        dev = d[0].device
+        for t_ in d:
+            if t_.numel() != nq or t_.dtype != torch.float32 or not t_.is_contiguous() or t_.device != dev:
+                raise SDMMError("planes: contiguous float32 device tensors of one value per direction")
+        rgb = [torch.empty(nq, device=dev) for _ in range(3)]
+        s_ = torch.cuda.current_stream(dev) if stream is None else stream
+        _check(lib().sdmm_env_eval(self.h, nq, C.cast((C.c_void_p * 3)(*[x.data_ptr() for x in d]), C.c_void_p),
+                                   C.cast((C.c_void_p * 3)(*[x.data_ptr() for x in rgb]), C.c_void_p),
+                                   C.c_void_p(int(s_.cuda_stream) or None)))
+        return rgb
 
     def render(self, tree: "STree", node_mix=None, spp: int = 1, max_depth: int = 10, rr_depth: int = 10,
                guided: bool = False, bsdf_fraction: float = 0.5, saved_vertices: int = 9, seed: int = 0,

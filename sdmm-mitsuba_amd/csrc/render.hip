@@ -27,7 +27,9 @@
 // over a diffuse base, the lobe chosen by Fresnel-weighted probability), rough
 // conductors, Phong BSDFs (bsdf_phong.h) and rough dielectrics
 // (bsdf_roughdielectric.h: the one two-sided, transmitting material), one-
-// sided area emitters (area.cpp: Le = radiance on the normal side).  No NEE (the plugin's
+// sided area emitters (area.cpp: Le = radiance on the normal side) and an
+// optional environment emitter (envmap.h: constant or lat-long map, seen by
+// every ray that leaves the scene).  No NEE (the plugin's
 // NEE block is compiled out, :700-734; emitterPdf = 0, MIS weight 1, :811-816).
 //
 // Random numbers: counter-based (rng_uniform below), one fixed slot per
@@ -212,7 +214,10 @@ __device__ __forceinline__ void record_radiance(const PathsDev& P, int64_t p, in
 // ---------------------------------------------------------------------------
 // camera rays: pixel = path / spp (box filter, uniform jitter), Mitsuba's
 // perspective mapping (fov along x): local d = ((1 - 2 sx) tan, (1 - 2 sy) tan / aspect, 1)
-template <bool MESH>
+// ENV: the variant for a scene with an environment emitter (envmap.h): a ray
+// that hits nothing returns evalEnvironment (sdmm_proc.cpp:659-671); the other
+// scenes' kernels do not carry the lookup and keep their registers.
+template <bool MESH, bool ENV>
 __global__ void __launch_bounds__(256)
 li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -248,9 +253,12 @@ li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) 
         if (qe >= 0 && -dot3(d, qn) > 0.0f)
             for (int ch = 0; ch < 3; ++ch) L[ch] = S.rad[3 * qe + ch];
     }
+    // no hit: the environment seen directly (:659-671; throughput 1, no vertex yet)
+    if constexpr (ENV)
+        if (q < 0) env_eval<true>(S.env, d, L);
     P.lr[i] = L[0]; P.lg[i] = L[1]; P.lb[i] = L[2];
     P.quad[i] = q;
-    P.depth[i] = q >= 0 ? 1 : -1;   // no hit: no environment emitter, the path ends
+    P.depth[i] = q >= 0 ? 1 : -1;   // no hit: the path ends (with the environment's radiance, if any)
 }
 
 // ---------------------------------------------------------------------------
@@ -476,7 +484,10 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
 // The wavefront marks a query whose BSDF sample was chosen comp == -2 (valid
 // conditional) -- the plain bounce's pdf_mode and the product bounce's
 // choice <= h alike.
-template <bool PHONG, bool DIEL, bool MESH>
+// ENV: the variant for a scene with an environment emitter, as the camera
+// kernel's: a bounce ray that hits nothing brings evalEnvironment(wo) into
+// `value` (rayIntersectAndLookForEmitter, :1047-1051) and the path ends.
+template <bool PHONG, bool DIEL, bool MESH, bool ENV>
 __global__ void __launch_bounds__(256)
 li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int rr_depth, float h,
                 uint64_t seed, int product) {
@@ -643,6 +654,8 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         if (he >= 0 && -dot3(wo, prim_n<MESH>(S, q)) > 0.0f)
             for (int ch = 0; ch < 3; ++ch) value[ch] = S.rad[3 * he + ch];
     }
+    if constexpr (ENV)
+        if (q < 0) env_eval<true>(S.env, wo, value);
     int nv = P.nv[i];
     if (value[0] != 0.0f || value[1] != 0.0f || value[2] != 0.0f) {
         const float rad[3] = {thr[0] * value[0], thr[1] * value[1], thr[2] * value[2]};
@@ -856,10 +869,18 @@ static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256)
                         : ((S).has_phong ? kernel<true, false, M> : kernel<false, false, M>))
 #define LI_VARIANT(kernel, S) ((S).has_mesh ? LI_VARIANT_M(kernel, S, true) : LI_VARIANT_M(kernel, S, false))
 
+// the camera and shade kernels' ENV variants: a scene with an environment emitter
+#define LI_VARIANT_ME(kernel, S, M, E)                                                           \
+    ((S).has_dielectric ? ((S).has_phong ? kernel<true, true, M, E> : kernel<false, true, M, E>) \
+                        : ((S).has_phong ? kernel<true, false, M, E> : kernel<false, false, M, E>))
+#define LI_VARIANT_E(kernel, S, E) \
+    ((S).has_mesh ? LI_VARIANT_ME(kernel, S, true, E) : LI_VARIANT_ME(kernel, S, false, E))
+
 hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, int64_t path0, int spp, uint64_t seed,
                             hipStream_t st) {
-    hipLaunchKernelGGL((S.has_mesh ? li_camera_kernel<true> : li_camera_kernel<false>), grid_for(P.P), dim3(256), 0, st,
-                       S, P, path0, spp, seed);
+    auto kernel = S.env.kind != kEnvNone ? (S.has_mesh ? li_camera_kernel<true, true> : li_camera_kernel<false, true>)
+                                         : (S.has_mesh ? li_camera_kernel<true, false> : li_camera_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid_for(P.P), dim3(256), 0, st, S, P, path0, spp, seed);
     return hipGetLastError();
 }
 hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
@@ -887,8 +908,27 @@ hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDe
 
 hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
                            int rr_depth, float h, uint64_t seed, int product, hipStream_t st) {
-    hipLaunchKernelGGL(LI_VARIANT(li_shade_kernel, S), grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce,
-                       rr_depth, h, seed, product);
+    auto kernel = S.env.kind != kEnvNone ? LI_VARIANT_E(li_shade_kernel, S, true) : LI_VARIANT_E(li_shade_kernel, S, false);
+    hipLaunchKernelGGL(kernel, grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce, rr_depth, h, seed, product);
+    return hipGetLastError();
+}
+
+// sdmm_env_eval: evalEnvironment of nq directions on device planes
+__global__ void __launch_bounds__(256)
+env_eval_kernel(EnvDev E, int64_t nq, const float* __restrict__ d0, const float* __restrict__ d1,
+                const float* __restrict__ d2, float* __restrict__ r, float* __restrict__ g, float* __restrict__ b) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const float d[3] = {d0[i], d1[i], d2[i]};
+    float rgb[3];
+    env_eval<true>(E, d, rgb);
+    r[i] = rgb[0]; g[i] = rgb[1]; b[i] = rgb[2];
+}
+hipError_t launch_env_eval(const SceneDev& S, int64_t nq, const float* const d[3], float* const rgb[3],
+                           hipStream_t st) {
+    if (nq <= 0) return hipSuccess;
+    hipLaunchKernelGGL(env_eval_kernel, grid_for(nq), dim3(256), 0, st, S.env, nq, d[0], d[1], d[2], rgb[0], rgb[1],
+                       rgb[2]);
     return hipGetLastError();
 }
 // getDMM + rotate_to_wo for a batch of local incident directions against one

@@ -38,6 +38,8 @@ hipError_t launch_li_film(const PathsDev& P, int64_t pix0, int64_t npix, int spp
                           float* image_sqr, hipStream_t st);
 hipError_t launch_scene_intersect(const SceneDev& S, int64_t nq, const float* const o[3], const float* const d[3],
                                   float mint, float maxt, int mode, int32_t* prim, float* t, hipStream_t st);
+hipError_t launch_env_eval(const SceneDev& S, int64_t nq, const float* const d[3], float* const rgb[3],
+                           hipStream_t st);
 hipError_t launch_roughdielectric(const float* bp, const float st[3], int64_t nq, const float* const wi[3],
                                   const float* const* u, float* const wo[3], float* const value[3], float* pdf,
                                   float* eta_out, hipStream_t st_);
@@ -68,6 +70,7 @@ struct sdmm_scene {
     BvhNode* dnodes = nullptr;   // the triangle mesh (mesh_bvh.h), null without one
     MeshTri* dtris = nullptr;
     MeshHit* dhits = nullptr;
+    EnvTexel* denv = nullptr;    // the lat-long environment map (envmap.h), null without one
     float smin[3] = {0, 0, 0}, snorm = 1.0f, tmin[3] = {0, 0, 0}, tmax[3] = {0, 0, 0};
     // per-render buffers (grown)
     void* buf = nullptr;
@@ -224,6 +227,42 @@ bool geometry_args_ok(const sdmm_scene_desc* d) {
 // some primitive may carry an emitter index (quads' or triangles' array set):
 // the radiance table is needed, uploaded and read then
 bool has_emitters(const sdmm_scene_desc* d) { return d->emitter || (d->n_triangles > 0 && d->tri_emitter); }
+
+// the description's environment emitter, validated; *E gets every field but
+// the texel pointer.  0, or the error code (message set).
+int prep_env(const sdmm_scene_desc* d, const char* who, EnvDev* E) {
+    const std::string w(who);
+    *E = EnvDev{};
+    if (d->env_kind < kEnvNone || d->env_kind > kEnvLatLong)
+        return fail(SDMM_E_INVALID, w + ": env_kind outside 0..2");
+    E->kind = d->env_kind;
+    if (d->env_kind == kEnvConstant) {
+        for (int c = 0; c < 3; ++c) {
+            if (!(std::isfinite(d->env_radiance[c]) && d->env_radiance[c] >= 0.0f))
+                return fail(SDMM_E_INVALID, w + ": a non-finite or negative env_radiance");
+            E->rad[c] = d->env_radiance[c];
+        }
+    } else if (d->env_kind == kEnvLatLong) {
+        if (!d->env_pixels) return fail(SDMM_E_INVALID, w + ": a lat-long environment without env_pixels");
+        if (d->env_width < 1 || d->env_height < 1)
+            return fail(SDMM_E_INVALID, w + ": env_width or env_height < 1");
+        const int64_t n = (int64_t)d->env_width * d->env_height;
+        if (n > kEnvMaxTexels) return fail(SDMM_E_INVALID, w + ": an environment map of more than 2^26 texels");
+        if (!(std::isfinite(d->env_scale) && d->env_scale >= 0.0f))
+            return fail(SDMM_E_INVALID, w + ": a non-finite or negative env_scale");
+        for (int i = 0; i < 9; ++i)
+            if (!std::isfinite(d->env_world_to_local[i]))
+                return fail(SDMM_E_INVALID, w + ": a non-finite env_world_to_local entry");
+        for (int64_t i = 0; i < 3 * n; ++i)
+            if (!(std::isfinite(d->env_pixels[i]) && d->env_pixels[i] >= 0.0f))
+                return fail(SDMM_E_INVALID, w + ": a non-finite or negative environment texel");
+        E->w = d->env_width;
+        E->h = d->env_height;
+        E->scale = d->env_scale;
+        for (int i = 0; i < 9; ++i) E->m[i] = d->env_world_to_local[i];
+    }
+    return SDMM_OK;
+}
 
 // the quads' derived data (normal, duals) and their corners' AABB, after the
 // description's argument checks.  0, or the error code (message set).
@@ -386,6 +425,16 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
             mx[a] = std::max(mx[a], mesh.mx[a]);
         }
     }
+    // the environment emitter: validated, a lat-long map as RGBA texels (envmap.h)
+    EnvDev env;
+    rc = prep_env(d, "sdmm_scene_create", &env);
+    if (rc) return rc;
+    std::vector<EnvTexel> env_texels;
+    if (env.kind == kEnvLatLong) {
+        env_texels.resize((size_t)env.w * (size_t)env.h);
+        for (size_t i = 0; i < env_texels.size(); ++i)
+            env_texels[i] = EnvTexel{d->env_pixels[3 * i], d->env_pixels[3 * i + 1], d->env_pixels[3 * i + 2], 0.0f};
+    }
     sdmm_scene* s = new (std::nothrow) sdmm_scene();
     if (!s) return fail(SDMM_E_NOMEM, "out of host memory");
     s->device = device;
@@ -423,6 +472,9 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
         e = hipMemcpy(s->dtris, mesh.tris.data(), sizeof(MeshTri) * mesh.tris.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess && d->n_triangles > 0)
         e = hipMemcpy(s->dhits, mesh.hits.data(), sizeof(MeshHit) * mesh.hits.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !env_texels.empty()) e = hipMalloc(&s->denv, sizeof(EnvTexel) * env_texels.size());
+    if (e == hipSuccess && !env_texels.empty())
+        e = hipMemcpy(s->denv, env_texels.data(), sizeof(EnvTexel) * env_texels.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc(&s->drefl, sizeof(float) * 3 * (size_t)d->n_bsdfs);
     if (e == hipSuccess && has_emitters(d)) e = hipMalloc(&s->drad, sizeof(float) * 3 * (size_t)d->n_emitters);
     if (e == hipSuccess && d->bsdf_params)
@@ -469,6 +521,8 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
             if (d->bsdf_params[kBsdfParams * b] == (float)kBsdfDielectric) S.has_dielectric = 1;
         }
     S.rad = s->drad;
+    S.env = env;
+    S.env.texels = reinterpret_cast<const float*>(s->denv);
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 4; ++c) S.cam[4 * r + c] = d->camera_to_world[4 * r + c];
     S.tanx = (float)std::tan(0.5 * (double)d->fov_x_deg * 3.14159265358979323846 / 180.0);
@@ -661,6 +715,7 @@ void sdmm_scene_destroy(sdmm_scene* s) {
     if (s->dnodes) (void)hipFree(s->dnodes);
     if (s->dtris) (void)hipFree(s->dtris);
     if (s->dhits) (void)hipFree(s->dhits);
+    if (s->denv) (void)hipFree(s->denv);
     if (s->buf) (void)hipFree(s->buf);
     if (s->lt) (void)hipFree(s->lt);
     if (s->hcount) (void)hipHostFree(s->hcount);
@@ -716,6 +771,31 @@ int sdmm_scene_intersect_host(const sdmm_scene_desc* desc, int64_t nq, const flo
         prim[i] = best;
         t[i] = tb;
     }
+    _mm_setcsr(csr);
+    return SDMM_OK;
+}
+
+int sdmm_env_eval(const sdmm_scene* s, int64_t nq, const float* const d[3], float* const rgb[3], void* hip_stream) {
+    if (!s || nq < 0) return fail(SDMM_E_INVALID, "sdmm_env_eval: invalid argument");
+    if (nq == 0) return SDMM_OK;
+    if (!d || !d[0] || !d[1] || !d[2] || !rgb || !rgb[0] || !rgb[1] || !rgb[2])
+        return fail(SDMM_E_INVALID, "sdmm_env_eval: NULL plane");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(launch_env_eval(s->S, nq, d, rgb, (hipStream_t)hip_stream));
+    return SDMM_OK;
+}
+
+int sdmm_env_eval_host(const sdmm_scene_desc* desc, int64_t nq, const float* d, float* rgb) {
+    if (!desc || nq < 0 || (nq > 0 && (!d || !rgb)))
+        return fail(SDMM_E_INVALID, "sdmm_env_eval_host: invalid argument");
+    EnvDev env;
+    const int rc = prep_env(desc, "sdmm_env_eval_host", &env);
+    if (rc) return rc;
+    env.texels = desc->env_pixels;   // [h][w][3], read in place
+    // the device's float environment: denormals flushed (-fgpu-flush-denormals-to-zero)
+    const unsigned csr = _mm_getcsr();
+    _mm_setcsr(csr | 0x8040u);
+    for (int64_t i = 0; i < nq; ++i) env_eval<false>(env, d + 3 * i, rgb + 3 * i);
     _mm_setcsr(csr);
     return SDMM_OK;
 }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "mesh_bvh.h"
+#include "envmap.h"
 
 namespace sdmm {
 
@@ -75,6 +76,9 @@ struct SceneDev {
     int n_tris;
     int has_mesh;         // the Li kernels' MESH variants run
     int mesh_brute;       // SDMM_MESH_BRUTE=1: the loop over all triangles instead of the BVH (A/B)
+    // environment emitter (envmap.h): kind 0 without one; otherwise the camera
+    // and shade kernels' ENV variants run
+    EnvDev env;
 };
 
 // closest quad with t in (mint, maxt), the lowest id on equal t (strict <);

@@ -674,7 +674,8 @@ private:
 // pdfSurface's mixing of BSDF and guiding densities (sdmm_proc.cpp:587-589):
 // pdf = h * bsdfPdf + (1 - h) * gmmPdf, h = 0.5 (0.3 with product sampling).
 // An analytic scene for the device Li (sdmm_scene_*): the description's
-// arrays are only read during construction.
+// arrays are only read during construction (its environment map included:
+// sdmm_scene_desc's env fields).
 class Scene {
 public:
     Scene(const sdmm_scene_desc& desc, int device = 0) { check(sdmm_scene_create(&desc, device, &h_), "sdmm_scene_create"); }
@@ -685,6 +686,10 @@ public:
     // render() (volpath_sdmm.cpp:375-393): scene_norm.json values and the tree box
     void normalization(float scene_min[3], float* spatial_norm, float tree_min[3], float tree_max[3]) const {
         check(sdmm_scene_normalization(h_, scene_min, spatial_norm, tree_min, tree_max), "sdmm_scene_normalization");
+    }
+    // evalEnvironment of nq directions on device planes (asynchronous on hip_stream)
+    void env_eval(int64_t nq, const float* const d[3], float* const rgb[3], void* hip_stream = nullptr) const {
+        check(sdmm_env_eval(h_, nq, d, rgb, hip_stream), "sdmm_env_eval");
     }
 
 private:

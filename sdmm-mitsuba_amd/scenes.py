@@ -401,15 +401,61 @@ def _look_at(origin, target, up):
     return M.reshape(-1).astype(np.float32)
 
 
-def torus_scene(width=640, height=360, nu=96, nv=48, glass=True):
+def constant_environment(rgb):
+    """The description fields of a `constant` environment emitter
+    (emitters/constant.cpp): every ray that leaves the scene sees the radiance
+    rgb."""
+    return {"env_kind": 1, "env_radiance": np.asarray(rgb, np.float32).reshape(3)}
+
+
+def latlong_direction(u, v):
+    """The unit direction (emitter's local frame) of the lat-long texture
+    coordinates (u, v) in [0, 1)^2 of a kind-2 environment -- the inverse of
+    envmap.cpp:385-388's mapping u = atan2(x, -z) / 2 pi (mod 1), v = acos(y)
+    / pi: row 0 of the map is the +y pole, u = 0 looks along -z."""
+    u, v = np.asarray(u, np.float64), np.asarray(v, np.float64)
+    phi, theta = 2.0 * np.pi * u, np.pi * v
+    return np.stack([np.sin(theta) * np.sin(phi), np.cos(theta), -np.sin(theta) * np.cos(phi)], -1)
+
+
+def sky_environment(width=256, height=128, sun_dir=(0.35, 0.8, 0.45), sun_radius_deg=4.0,
+                    sun_radiance=(180.0, 165.0, 140.0), zenith=(0.25, 0.45, 0.9), horizon=(0.9, 0.9, 0.85),
+                    to_world=None):
+    """The description fields of a lat-long environment map holding a
+    procedural sky: a zenith-to-horizon gradient (horizon colour below the
+    horizon, dimmed to a third: the ground's bounce) plus a sun disc of
+    sun_radius_deg about sun_dir with a smooth edge of a quarter of the radius.
+    A stand-in for the Torus and Kitchen configurations' `sunsky` emitter, as
+    the torus is for their geometry: Mitsuba's sun / sky model and its tables
+    are not restated.  to_world: the emitter's 3x3 rotation (default the
+    identity); the description carries its inverse."""
+    uu, vv = np.meshgrid((np.arange(width) + 0.5) / width, (np.arange(height) + 0.5) / height)
+    d = latlong_direction(uu, vv)                                     # [h, w, 3]
+    up = np.clip(d[..., 1], 0.0, 1.0)[..., None]
+    sky = np.asarray(horizon, np.float64) + (np.asarray(zenith, np.float64) - np.asarray(horizon, np.float64)) * up ** 0.5
+    px = np.where(d[..., 1:2] >= 0.0, sky, np.asarray(horizon, np.float64) / 3.0)
+    sun = np.asarray(sun_dir, np.float64)
+    sun = sun / np.linalg.norm(sun)
+    ang = np.degrees(np.arccos(np.clip(d @ sun, -1.0, 1.0)))
+    disc = np.clip((sun_radius_deg * 1.25 - ang) / (0.25 * sun_radius_deg), 0.0, 1.0)[..., None]
+    px = px + disc * np.asarray(sun_radiance, np.float64)
+    R = np.eye(3) if to_world is None else np.asarray(to_world, np.float64).reshape(3, 3)
+    return {"env_kind": 2, "env_pixels": np.ascontiguousarray(px, np.float32), "env_scale": 1.0,
+            "env_world_to_local": np.linalg.inv(R).astype(np.float32).reshape(-1)}
+
+
+def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=None):
     """The Torus configuration's stand-in (test-suite/scenes/torus/torus.xml):
     a diffuse torus (reflectance .8, .8, .4; torus_mesh(nu, nv), R 1, r 0.4,
     lying on the floor) under a rough-dielectric case of quads (alpha 0.05,
     ior 1.5, the shipped dielectric_4c learned model) on a diffuse floor.  The
-    reference lights the scene with `sunsky`; the device Li has no environment
-    emitter, so a closed room of quads with a ceiling lamp is the stated
-    proxy.  The camera follows torus.xml's framing loosely: above and in front
-    of the case, looking down at the torus."""
+    reference lights the scene with `sunsky`.  environment: the env fields of
+    the description (constant_environment / sky_environment) -- the scene is
+    then open, the torus under its case on the floor under that sky, with no
+    room and no lamp.  None (the default): a closed room of quads with a
+    ceiling lamp, the proxy from before the device Li had an environment
+    emitter.  The camera follows torus.xml's framing loosely: above and in
+    front of the case, looking down at the torus."""
     names = ["Room", "Floor", "Torus", "Glass", "Light"]
     refl = {"Room": (0.6, 0.6, 0.6), "Floor": (0.5, 0.5, 0.5), "Torus": (0.8, 0.8, 0.4), "Glass": (1.0, 1.0, 1.0),
             "Light": (0.0, 0.0, 0.0)}
@@ -425,11 +471,15 @@ def torus_scene(width=640, height=360, nu=96, nv=48, glass=True):
                 continue
             quads.append(np.concatenate((p0, e2, e1) if inward else (p0, e1, e2)))
             bsdf.append(names.index(name)); emitter.append(-1)
-    box((-4.0, 0.0, -4.0), (4.0, 5.0, 4.0), "Room", inward=True, skip_bottom=True)
+    if environment is None:
+        box((-4.0, 0.0, -4.0), (4.0, 5.0, 4.0), "Room", inward=True, skip_bottom=True)
     quads.append(np.array([-4.0, 0.0, -4.0, 0.0, 0.0, 8.0, 8.0, 0.0, 0.0]))      # floor, normal +y
     bsdf.append(names.index("Floor")); emitter.append(-1)
-    quads.append(np.array([-1.5, 4.99, -1.5, 3.0, 0.0, 0.0, 0.0, 0.0, 3.0]))     # lamp, normal -y
-    bsdf.append(names.index("Light")); emitter.append(0)
+    if environment is None:
+        quads.append(np.array([-1.5, 4.99, -1.5, 3.0, 0.0, 0.0, 0.0, 0.0, 3.0]))     # lamp, normal -y
+        bsdf.append(names.index("Light")); emitter.append(0)
+    else:
+        extra_env = dict(environment)
     bp = np.zeros((len(names), 8), np.float32)
     extra = {}
     if glass:
@@ -440,6 +490,8 @@ def torus_scene(width=640, height=360, nu=96, nv=48, glass=True):
         extra["learned_models_nd"] = [model if nm == "Glass" else None for nm in names]
     T = np.array([[1.0, 0, 0, 0], [0, 1.0, 0, 0.45], [0, 0, 1.0, 0]])
     verts, tris = torus_mesh(nu, nv, 1.0, 0.4, to_world=T)
+    if environment is not None:
+        extra.update(extra_env)
     return {**extra,
         "quads": np.asarray(quads, np.float32).reshape(-1),
         "bsdf": np.asarray(bsdf, np.int32),

@@ -11,6 +11,12 @@
                    96x48) through the same loop; SDMM_MESH_BRUTE=1 in the
                    environment makes the Li kernels loop over all triangles
                    instead of walking the BVH (A/B)
+--env              with --torus: the open scene -- no room, no lamp, the torus
+                   under its case on the floor under scenes.sky_environment()
+                   (a lat-long environment map)
+--env-eval N       time sdmm_env_eval on 2^N random directions against a
+                   1024x512 map (device time per launch from events); with
+                   --repeat 0 nothing else runs
 --intersect N      with --torus: also time sdmm_scene_intersect on 2^N
                    camera-like rays against the scene without its case, BVH
                    and brute force (rays/s), and a plain unguided 8-spp pass;
@@ -43,6 +49,8 @@ if __name__ == "__main__":
     ap.add_argument("--torus", action="store_true", help="the torus scene (triangle mesh) instead of the Cornell box")
     ap.add_argument("--tess", default="96x48", help="--torus: tessellation NUxNV")
     ap.add_argument("--intersect", type=int, default=0, help="--torus: time Scene.intersect on 2^N rays")
+    ap.add_argument("--env", action="store_true", help="--torus: the open scene under a sky environment map")
+    ap.add_argument("--env-eval", type=int, default=0, help="time Scene.env_eval on 2^N directions, 1024x512 map")
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--summary", action="store_true", help="one line per run, no per-iteration lines")
     a = ap.parse_args()
@@ -55,12 +63,41 @@ if __name__ == "__main__":
         scenes = importlib.import_module("sdmm_mitsuba_amd.scenes")
         scenes.cornell_box = functools.partial(scenes.cornell_box, dielectric=tuple(a.dielectric),
                                                dielectric_lift=0.02)
+    if a.env and not a.torus:
+        ap.error("--env goes with --torus")
+    if a.env_eval:
+        import numpy as np
+        scenes = importlib.import_module("sdmm_mitsuba_amd.scenes")
+        dev = torch.device("cuda", 0)
+        sc = pkg.Scene(scenes.torus_scene(64, 36, 24, 12, environment=scenes.sky_environment(1024, 512)))
+        n = 1 << a.env_eval
+        g = torch.Generator(device=dev).manual_seed(1)
+        dirs = torch.randn(n, 3, device=dev, generator=g)
+        dirs = dirs / dirs.norm(dim=1, keepdim=True)
+        d = [dirs[:, i].contiguous() for i in range(3)]
+        launches = 20
+        sc.env_eval(d)
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(launches):
+                rgb = sc.env_eval(d)
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) / launches)
+        print(json.dumps({"env_eval": "1024x512", "directions": n, "launches_per_group": launches,
+                          "ms": [round(t, 4) for t in times], "directions_per_s": n / (min(times) * 1e-3),
+                          "mean_radiance": float(torch.stack(rgb).mean())}), flush=True)
     if a.torus:
         import os
         import time
         scenes = importlib.import_module("sdmm_mitsuba_amd.scenes")
         nu, nv = (int(x) for x in a.tess.lower().split("x"))
-        scenes.cornell_box = lambda w, h, **kw: scenes.torus_scene(w, h, nu, nv)
+        sky = scenes.sky_environment() if a.env else None
+        scenes.cornell_box = lambda w, h, **kw: (scenes.torus_scene(w, h, nu, nv, environment=sky) if a.env
+                                                 else scenes.torus_scene(w, h, nu, nv))
         brute = os.environ.get("SDMM_MESH_BRUTE") == "1"
         if a.intersect:
             dev = torch.device("cuda", 0)
@@ -95,8 +132,8 @@ if __name__ == "__main__":
                                   "launches_per_group": launches, "ms": [round(t, 4) for t in times],
                                   "rays_per_s": n / (min(times) * 1e-3),
                                   "mesh_hits": int((prim >= sc.n_quads).sum())}), flush=True)
-            # a plain unguided pass (8 spp, no training) of the scene with its case
-            sc = pkg.Scene(scenes.torus_scene(640, 360, nu, nv))
+            # a plain unguided pass (8 spp, no training) of the scene with its case (--env: the open scene)
+            sc = pkg.Scene(scenes.cornell_box(640, 360))
             _, _, tmin, tmax = sc.normalization()
             tree = pkg.STree(tmin, tmax)
             tree.split_to_depth(2)
@@ -108,7 +145,7 @@ if __name__ == "__main__":
                 torch.cuda.synchronize()
                 times.append(time.perf_counter() - t0)
             print(json.dumps({"unguided_pass_ms": [round(t * 1e3, 3) for t in times[1:]], "triangles": 2 * nu * nv,
-                              "mesh": "brute" if brute else "bvh"}), flush=True)
+                              "mesh": "brute" if brute else "bvh", "env": bool(a.env)}), flush=True)
     for K in a.K:
       for mode in a.modes:
         for _ in range(a.repeat):
@@ -116,7 +153,8 @@ if __name__ == "__main__":
                                       product=a.product, glossy=tuple(a.glossy))
             if a.torus:
                 out["workload"] = out["workload"].replace("Cornell Box", f"Torus scene ({a.tess}, " +
-                                                          ("brute force" if brute else "BVH") + ")")
+                                                          ("brute force" if brute else "BVH") +
+                                                          (", open under a sky map" if a.env else "") + ")")
                 its = out["iterations"]
                 out["first_pass_ms"] = round(its[0]["ms"], 3)     # unguided render + push + optimize
                 out["guided_pass_ms"] = [round(x["ms"], 3) for x in its if not x["train"]]

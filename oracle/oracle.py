@@ -640,6 +640,40 @@ def li_intersect(desc, o, d, mint=1e-4, maxt=float("inf")):
     return prim, t
 
 
+def _env_args(desc):
+    """The environment emitter of a description (the keys pkg.Scene reads,
+    with its defaults: env_kind 0, env_scale 1, env_world_to_local the
+    identity) as ctypes arguments in or_env_eval's order, and the arrays they
+    point into (kept alive by the caller)."""
+    kind = int(desc.get("env_kind", 0))
+    rad = desc.get("env_radiance")
+    rad = np.ascontiguousarray(rad, np.float32).reshape(3) if rad is not None else None
+    px = np.ascontiguousarray(desc["env_pixels"], np.float32) if desc.get("env_pixels") is not None else None
+    if px is not None:
+        assert px.ndim == 3 and px.shape[2] == 3, "env_pixels: an array [height, width, 3]"
+    h, w = (0, 0) if px is None else px.shape[:2]
+    m = desc.get("env_world_to_local")
+    m = np.eye(3, dtype=np.float32).reshape(-1) if m is None else np.ascontiguousarray(m, np.float32).reshape(9)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    args = (C.c_int(kind), vp(rad), vp(px), C.c_int(w), C.c_int(h), C.c_float(float(desc.get("env_scale", 1.0))),
+            vp(m))
+    return args, (rad, px, m)
+
+
+def env_eval(env_desc, d):
+    """or_env_eval: Emitter::evalEnvironment (sdmm_oracle_li.inc) of the
+    environment emitter in a description's env_* keys for directions d ([n,
+    3], used as given) -> float32 [n, 3]; 0 without an environment."""
+    args, keep = _env_args(env_desc)
+    dd = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    rgb = np.empty((len(dd), 3), np.float32)
+    f = lib().or_env_eval
+    f.restype = C.c_int
+    rc = f(*args, C.c_int64(len(dd)), dd.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p))
+    assert rc == 0, "or_env_eval: not a valid environment emitter"
+    return rgb
+
+
 def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_depth=10, rr_depth=10, h=0.5,
               V=9, seed=0, pixels=None, learned=None, threads=1, rr_eta_one=False):
     """SDMMRenderer::Li restated on the CPU (sdmm_oracle_li.inc) for a
@@ -650,11 +684,17 @@ def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_d
     the conductors' SDMM4s / the Phong BSDFs' and rough dielectrics' SDMM5s;
     desc["mesh_vertices"] / ["triangles"] / ["tri_bsdf"] / ["tri_emitter"] /
     ["tri_flip_normals"]: the triangle mesh (a description may have no quads).
+    desc["env_kind"] / ["env_radiance"] / ["env_pixels"] / ["env_scale"] /
+    ["env_world_to_local"]: the environment emitter, as pkg.Scene reads them; a
+    description without an emitter quad needs no "emitter" / "radiance".
     rr_eta_one: a switch for the tests alone -- roulette with the path's
     relative index taken as 1.  Returns dict image (3, H, W), image_sqr, rec
     (16, V, P), nv (P,), comps (bounces, P), hit_bsdf (bounces, P): the BSDF
     each live bounce scattered at (-1: none), inside (bounces, P): 1 where
-    that bounce met the surface from behind, 0 from the front, -1 none."""
+    that bounce met the surface from behind, 0 from the front, -1 none,
+    escaped (bounces + 1, P): row 0 the camera ray, row b + 1 bounce b's ray --
+    1 where it left the scene (the environment, if any, was evaluated), 0
+    where it hit something, -1 no ray."""
     W, H = int(desc["width"]), int(desc["height"])
     lo, hi = (0, W * H) if pixels is None else pixels
     P = (hi - lo) * spp
@@ -662,7 +702,11 @@ def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_d
     i32 = lambda a: np.ascontiguousarray(a, np.int32)
     quads, flip, bsdf, em, nq = _quad_args(desc)
     mesh = _mesh_args(desc)
-    refl, rad = f32(desc["reflectance"]), f32(desc["radiance"])
+    refl = f32(desc["reflectance"])
+    rad = f32(desc["radiance"]) if desc.get("radiance") is not None else None
+    emitters = [e for e in (em, mesh[5]) if e is not None]
+    assert rad is not None or all((e < 0).all() for e in emitters), "an emitter without desc['radiance']"
+    env, env_keep = _env_args(desc)
     cam = f32(desc["camera_to_world"])
     mn = np.ascontiguousarray(np.asarray(aabb)[:, :3].reshape(-1), np.float32)
     mx = np.ascontiguousarray(np.asarray(aabb)[:, 3:].reshape(-1), np.float32)
@@ -683,6 +727,7 @@ def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_d
     comps = np.full((bounces, P), -9, np.int32)
     hit_bsdf = np.full((bounces, P), -1, np.int32)
     inside = np.full((bounces, P), -1, np.int32)
+    escaped = np.full((bounces + 1, P), -1, np.int32)
     if learned is not None:
         bw, bm, bc, bd = f32(learned[0]), f32(learned[1]), f32(learned[2]), np.ascontiguousarray(learned[3], np.uint8)
         M = bw.shape[1]
@@ -704,7 +749,8 @@ def li_render(desc: dict, aabb, child, node_mix=None, guided=False, spp=1, max_d
            vp(bw), vp(bm), vp(bc), vp(bd), C.c_int(M), C.c_int(kmax), vp(image), vp(image_sqr), vp(rec), vp(nv),
            vp(comps), C.c_int(threads), vp(lmod) if lmod is not None else None,
            vp(lmod_nd) if lmod_nd is not None else None, vp(hit_bsdf), vp(mesh[0]), C.c_int(mesh[1]), vp(mesh[2]),
-           C.c_int(mesh[3]), vp(mesh[4]), vp(mesh[5]), vp(mesh[6]), vp(inside), C.c_int(int(rr_eta_one)))
+           C.c_int(mesh[3]), vp(mesh[4]), vp(mesh[5]), vp(mesh[6]), vp(inside), C.c_int(int(rr_eta_one)), *env,
+           vp(escaped))
     assert rc == 0, "or_li_render failed"
     return {"image": image, "image_sqr": image_sqr, "rec": rec, "nv": nv, "comps": comps, "hit_bsdf": hit_bsdf,
-            "inside": inside}
+            "inside": inside, "escaped": escaped}

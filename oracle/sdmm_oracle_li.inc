@@ -108,6 +108,17 @@
  * index (-1 no valid conditional, -2 the BSDF sample was chosen, -9 no query);
  * hit_bsdf[b * P + p]: the BSDF bounce b scattered at (-1: none); inside[b * P
  * + p]: 1 where it met the surface from behind, 0 from the front, -1 none.
+ *
+ * Environment emitters (`constant`, lat-long `envmap`): li_env_eval below,
+ * written from emitters/constant.cpp, envmap.cpp:380-393, :409 and mipmap.h
+ * :497-596 and not from the library's csrc/envmap.h -- the two are compared
+ * in tests/test_li_oracle_env.py.  A camera ray that hits nothing returns
+ * env(d) with throughput 1 and no vertex (sdmm_proc.cpp:659-671); a bounce ray
+ * that hits nothing sets value = env(wo) (:1047-1051), and radiance,
+ * recordRadiance and the saved vertex's weight follow as for an emitter hit;
+ * the path ends there, without a roulette draw.  escaped[(b + 1) * P + p]: 1
+ * where bounce b's ray left the scene, 0 where it hit something, -1 no ray;
+ * row 0 the camera ray.
  */
 #include <pthread.h>
 
@@ -123,6 +134,20 @@ typedef struct {
     int bsdf, emitter;
 } li_tri;
 
+/* the environment emitter (Scene::getEnvironmentEmitter): none, `constant`
+ * (emitters/constant.cpp) or a lat-long `envmap` (emitters/envmap.cpp) */
+#define LI_ENV_NONE 0
+#define LI_ENV_CONSTANT 1
+#define LI_ENV_LATLONG 2
+typedef struct {
+    int kind;
+    float rad[3];      /* constant: m_radiance */
+    const float* px;   /* envmap: [h][w][3], row 0 the +y pole (MIP level 0) */
+    int w, h;
+    float scale;       /* envmap: m_scale */
+    float inv[9];      /* envmap: the linear part of m_worldTransform's inverse, row major */
+} li_env;
+
 typedef struct {
     li_quad* quads;
     int nq;
@@ -133,6 +158,7 @@ typedef struct {
     const float* lmodel; /* LI_L4_STRIDE per BSDF: [M, M SDMM4 records]; NULL: no learned models */
     const float* lmodel_nd; /* LI_ND_STRIDE per BSDF: [C, M, M records of LI_ND_REC(C)]; NULL: none */
     const float* rad;
+    li_env env;
     float cam[12];
     float tanx, aspect, near_clip;
     int width, height;
@@ -313,6 +339,81 @@ int or_li_intersect(const float* quads, const int32_t* flip, int n_quads, const 
     free(S.quads);
     free(S.tris);
     return ok ? 0 : -1;
+}
+
+/* ---- environment emitters: Emitter::evalEnvironment ----
+ * constant.cpp: m_radiance whatever the ray.  envmap.cpp:380-393, :409 without
+ * ray differentials (this Li has none): v = toWorld^-1 d (d as given, no
+ * renormalisation); uv = (atan2(v.x, -v.z) INV_TWOPI, safe_acos(v.y) INV_PI);
+ * MIPMap::evalBilinear(0, uv) (mipmap.h:575-596); times m_scale.  Float; atan2
+ * and acos in double, rounded to float once. */
+
+/* MIPMap::evalTexel on level 0 (mipmap.h:497-563) with the envmap's boundary
+ * conditions: ERepeat along x (math::modulo, the positive remainder), EClamp
+ * along y */
+static const float* li_env_texel(const li_env* E, int x, int y) {
+    if (x < 0 || x >= E->w) {
+        x = x % E->w;
+        if (x < 0) x += E->w;
+    }
+    if (y < 0 || y >= E->h) y = y < 0 ? 0 : E->h - 1;
+    return E->px + 3 * ((size_t)y * (size_t)E->w + (size_t)x);
+}
+
+static void li_env_eval(const li_env* E, const float d[3], float out[3]) {
+    out[0] = out[1] = out[2] = 0.0f;
+    if (E->kind == LI_ENV_CONSTANT) {
+        for (int ch = 0; ch < 3; ++ch) out[ch] = E->rad[ch];
+        return;
+    }
+    if (E->kind != LI_ENV_LATLONG) return;
+    float v[3];
+    for (int r = 0; r < 3; ++r) v[r] = E->inv[3 * r] * d[0] + E->inv[3 * r + 1] * d[1] + E->inv[3 * r + 2] * d[2];
+    /* math::safe_acos: acos(std::min(1.0f, std::max(-1.0f, y))); std::max(a, b) is a < b ? b : a and std::min(a,
+     * b) is b < a ? b : a, so a NaN y becomes -1 */
+    float yc = -1.0f < v[1] ? v[1] : -1.0f;
+    yc = yc < 1.0f ? yc : 1.0f;
+    const float uvx = (float)atan2((double)v[0], (double)-v[2]) * 0.15915494309189533577f;
+    const float uvy = fl_acos(yc) * 0.31830988618379067154f;
+    if (!isfinite(uvx) || !isfinite(uvy)) return;   /* evalBilinear's guard: Value(0) */
+    const float u = uvx * (float)E->w - 0.5f, t = uvy * (float)E->h - 0.5f;
+    const int xp = (int)floorf(u), yp = (int)floorf(t);   /* math::floorToInt */
+    const float dx1 = u - (float)xp, dx2 = 1.0f - dx1;
+    const float dy1 = t - (float)yp, dy2 = 1.0f - dy1;
+    const float *a = li_env_texel(E, xp, yp), *b = li_env_texel(E, xp, yp + 1);
+    const float *c = li_env_texel(E, xp + 1, yp), *e = li_env_texel(E, xp + 1, yp + 1);
+    for (int ch = 0; ch < 3; ++ch)
+        out[ch] = (a[ch] * dx2 * dy2 + b[ch] * dx2 * dy1 + c[ch] * dx1 * dy2 + e[ch] * dx1 * dy1) * E->scale;
+}
+
+/* the env fields of a description (the keys pkg.Scene reads) -> li_env; 0: not a valid emitter */
+static int li_env_build(li_env* E, int kind, const float* radiance, const float* pixels, int w, int h, float scale,
+                        const float* world_to_local) {
+    memset(E, 0, sizeof(*E));
+    E->kind = kind;
+    if (kind == LI_ENV_NONE) return 1;
+    if (kind == LI_ENV_CONSTANT) {
+        if (!radiance) return 0;
+        for (int ch = 0; ch < 3; ++ch) E->rad[ch] = radiance[ch];
+        return 1;
+    }
+    if (kind != LI_ENV_LATLONG || !pixels || w < 1 || h < 1 || !world_to_local) return 0;
+    E->px = pixels;
+    E->w = w;
+    E->h = h;
+    E->scale = scale;
+    for (int k = 0; k < 9; ++k) E->inv[k] = world_to_local[k];
+    return 1;
+}
+
+/* ctypes entry for the tests: evalEnvironment of n directions (d, rgb: n x 3) */
+int or_env_eval(int kind, const float* radiance, const float* pixels, int w, int h, float scale,
+                const float* world_to_local, int64_t n, const float* d, float* rgb) {
+    FTZ_SCOPE;
+    li_env E;
+    if (!li_env_build(&E, kind, radiance, pixels, w, h, scale, world_to_local)) return -1;
+    for (int64_t i = 0; i < n; ++i) li_env_eval(&E, d + 3 * i, rgb + 3 * i);
+    return 0;
 }
 
 /* fresnelDielectricExt (libcore/util.cpp:651-681), the reflectance */
@@ -987,6 +1088,8 @@ typedef struct {
     int32_t* inside;     /* bounces x P, optional: 1 a live bounce met its surface from behind (wi . n < 0), 0
                             from the front, -1 no live bounce */
     int rr_eta_one;      /* tests only: roulette with the path's relative index taken as 1 */
+    int32_t* escaped;    /* (bounces + 1) x P, optional: row 0 the camera ray, row b + 1 bounce b's ray: 1 it left
+                            the scene (the environment, if any, was evaluated), 0 it hit something, -1 no ray */
     int bounces;
 } li_job;
 
@@ -1070,10 +1173,14 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
         for (int a = 0; a < 3; ++a) p[a] = o[a] + t * d[a];
         if (qe >= 0 && -li_dot3(d, li_prim_n(S, q)) > 0.0f)
             for (int ch = 0; ch < 3; ++ch) Li[ch] = S->rad[3 * qe + ch];
+    } else {
+        /* no intersection: the environment seen directly, throughput 1, no vertex (:659-671) */
+        li_env_eval(&S->env, d, Li);
     }
+    if (J->escaped) J->escaped[i] = q >= 0 ? 0 : 1;
     int depth = q >= 0 ? 1 : -1;
     for (int b = 0; b < J->bounces; ++b) {
-        int32_t comp_out = -9, bsdf_out = -1, inside_out = -1;
+        int32_t comp_out = -9, bsdf_out = -1, inside_out = -1, escaped_out = -1;
         if (depth >= 0) {
             /* loop head (:684-691), sampleSurface (:275-421) */
             int live = !(J->max_depth >= 0 && depth >= J->max_depth);
@@ -1310,7 +1417,11 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
                         const int he = li_prim_emitter(S, qh);
                         if (he >= 0 && -li_dot3(wo, li_prim_n(S, qh)) > 0.0f)
                             for (int ch = 0; ch < 3; ++ch) value[ch] = S->rad[3 * he + ch];
+                    } else {
+                        /* intersected nothing: value = env->evalEnvironment(ray) (:1047-1051) */
+                        li_env_eval(&S->env, wo, value);
                     }
+                    escaped_out = qh >= 0 ? 0 : 1;
                     if (value[0] != 0.0f || value[1] != 0.0f || value[2] != 0.0f) {
                         const float radv[3] = {thr[0] * value[0], thr[1] * value[1], thr[2] * value[2]};
                         for (int ch = 0; ch < 3; ++ch) Li[ch] += radv[ch];
@@ -1359,6 +1470,7 @@ static void li_path(const li_job* J, int64_t i, or_conditional* cd, or_product* 
         if (J->comps) J->comps[(int64_t)b * J->P + i] = comp_out;
         if (J->hit_bsdf) J->hit_bsdf[(int64_t)b * J->P + i] = bsdf_out;
         if (J->inside) J->inside[(int64_t)b * J->P + i] = inside_out;
+        if (J->escaped) J->escaped[(int64_t)(b + 1) * J->P + i] = escaped_out;
     }
     J->nv[i] = nv;
     for (int ch = 0; ch < 3; ++ch) J->L[3 * i + ch] = Li[ch];
@@ -1395,10 +1507,15 @@ int or_li_render(const float* quads, const int32_t* flip, const int32_t* bsdf, i
                  int32_t* comps, int nthreads, const float* learned_models, const float* learned_models_nd,
                  int32_t* hit_bsdf, const float* mesh_vertices, int n_mesh_vertices, const int32_t* triangles,
                  int n_triangles, const int32_t* tri_bsdf, const int32_t* tri_emitter, const int32_t* tri_flip,
-                 int32_t* inside, int rr_eta_one) {
+                 int32_t* inside, int rr_eta_one, int env_kind, const float* env_radiance, const float* env_pixels,
+                 int env_width, int env_height, float env_scale, const float* env_world_to_local,
+                 int32_t* escaped) {
     FTZ_SCOPE;
     li_scene S;
     memset(&S, 0, sizeof(S));
+    if (!li_env_build(&S.env, env_kind, env_radiance, env_pixels, env_width, env_height, env_scale,
+                      env_world_to_local))
+        return -1;
     if (!li_scene_build(&S, quads, flip, bsdf, n_quads, refl, bsdf_params, emitter, rad, cam, fov, near_clip, width,
                         height, mesh_vertices, n_mesh_vertices, triangles, n_triangles, tri_bsdf, tri_emitter,
                         tri_flip)) {
@@ -1428,7 +1545,7 @@ int or_li_render(const float* quads, const int32_t* flip, const int32_t* bsdf, i
             if ((kind == 2.0f || kind == 3.0f || kind == 4.0f) && J.lM < LI_L4_KEEP) J.lM = LI_L4_KEEP;
         }
     J.rec = rec; J.nv = nv; J.comps = comps; J.hit_bsdf = hit_bsdf;
-    J.inside = inside; J.rr_eta_one = rr_eta_one;
+    J.inside = inside; J.rr_eta_one = rr_eta_one; J.escaped = escaped;
     J.L = (float*)malloc(sizeof(float) * 3 * (size_t)(P > 0 ? P : 1));
     J.bounces = max_depth > 0 ? max_depth - 1 : V;
     if (nthreads < 1) nthreads = 1;

@@ -944,9 +944,10 @@ int sdmm_li_render(sdmm_scene* s, sdmm_stree* t, const sdmm_mix* const* node_mix
  * mode 1 loops over all triangles with the same triangle test
  * (Triangle::rayIntersect, core/triangle.h:109-145); the quads go through
  * their loop in both.  Both modes, here and on the host, are meant to return
- * bitwise the same (prim, t): the walk's cull carries a measured margin (1e-4
- * relative) against the triangle test's rounding, so this is tested on the
- * suite's rays and meshes, not proven for every input. */
+ * bitwise the same (prim, t): the walk's cull carries a margin (1e-4
+ * relative) against the triangle test's rounding, so this is tested inside
+ * an envelope ("Mesh: tested envelope": origins up to about 1e6
+ * triangle sizes away), not proven for every input. */
 int sdmm_scene_intersect(const sdmm_scene* s, int64_t nq, const float* const o[3], const float* const d[3], float mint,
                          float maxt, int mode, int32_t* prim, float* t, void* hip_stream);
 /* The same entirely on the host (no HIP call: runs without a GPU) from a
@@ -955,6 +956,11 @@ int sdmm_scene_intersect(const sdmm_scene* s, int64_t nq, const float* const o[3
  * it with the same traversal source. */
 int sdmm_scene_intersect_host(const sdmm_scene_desc* desc, int64_t nq, const float* o, const float* d, float mint,
                               float maxt, int mode, int32_t* prim, float* t);
+/* The same over a BVH whose inner levels are capped at max_levels (0: the
+ * traversal stack's 24, sdmm_scene_intersect_host's tree; a smaller cap as in
+ * sdmm_mesh_bvh_dump).  The hits do not depend on the cap. */
+int sdmm_scene_intersect_host_levels(const sdmm_scene_desc* desc, int max_levels, int64_t nq, const float* o,
+                                     const float* d, float mint, float maxt, int mode, int32_t* prim, float* t);
 /* evalEnvironment of the scene's environment emitter (sdmm_scene_desc's env
  * fields) for nq directions: d, rgb three device planes each (the direction
  * is used as given; rgb: the radiance, 0 for a scene without an environment).

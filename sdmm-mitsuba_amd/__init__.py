@@ -175,6 +175,8 @@ def lib():
                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdmm_scene_intersect_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                                 C.c_int, C.c_void_p, C.c_void_p]
+        L.sdmm_scene_intersect_host_levels.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                                       C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
         L.sdmm_env_eval.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdmm_env_eval_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.sdmm_mesh_bvh_dump.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
@@ -280,7 +282,8 @@ EXPORTED_SYMBOLS = [
     "sdmm_learned_conditional", "sdmm_learned_conditional_device", "sdmm_learned_save_json",
     "sdmm_learned_load_json", "sdmm_bsdf_phong_host",
     "sdmm_bsdf_roughdielectric_host", "sdmm_bsdf_roughdielectric_device",
-    "sdmm_scene_intersect", "sdmm_scene_intersect_host", "sdmm_mesh_bvh_dump",
+    "sdmm_scene_intersect", "sdmm_scene_intersect_host", "sdmm_scene_intersect_host_levels",
+    "sdmm_mesh_bvh_dump",
     "sdmm_env_eval", "sdmm_env_eval_host",
 ]
 
@@ -1331,11 +1334,12 @@ def env_eval_host(desc, d):
     return rgb
 
 
-def intersect_host(desc, o, d, mint=1e-4, maxt=float("inf"), mode=0):
+def intersect_host(desc, o, d, mint=1e-4, maxt=float("inf"), mode=0, max_levels=0):
     """sdmm_scene_intersect_host: the closest hit of rays o, d (numpy [nq, 3])
     against a description's quads and triangles, entirely on the host (no
-    GPU).  mode 0: the BVH, 1: the loop over all triangles.  (prim int32[nq],
-    -1 = none; t float32[nq], maxt without a hit)."""
+    GPU).  mode 0: the BVH, 1: the loop over all triangles.  max_levels: the
+    cap on the BVH's inner levels (0: the traversal stack's).  (prim
+    int32[nq], -1 = none; t float32[nq], maxt without a hit)."""
     sd, keep = _SceneDesc(), {}
     _fill_geometry(sd, desc, keep)
     o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
@@ -1344,8 +1348,9 @@ def intersect_host(desc, o, d, mint=1e-4, maxt=float("inf"), mode=0):
         raise SDMMError("o and d: [nq, 3] each")
     prim = np.empty(len(o), np.int32)
     t = np.empty(len(o), np.float32)
-    _check(lib().sdmm_scene_intersect_host(C.byref(sd), len(o), o.ctypes.data, dd.ctypes.data, float(mint),
-                                           float(maxt), int(mode), prim.ctypes.data, t.ctypes.data))
+    _check(lib().sdmm_scene_intersect_host_levels(C.byref(sd), int(max_levels), len(o), o.ctypes.data, dd.ctypes.data,
+                                                  float(mint), float(maxt), int(mode), prim.ctypes.data,
+                                                  t.ctypes.data))
     return prim, t
 
 

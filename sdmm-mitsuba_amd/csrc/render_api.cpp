@@ -749,7 +749,12 @@ int sdmm_scene_intersect(const sdmm_scene* s, int64_t nq, const float* const o[3
 
 int sdmm_scene_intersect_host(const sdmm_scene_desc* desc, int64_t nq, const float* o, const float* d, float mint,
                               float maxt, int mode, int32_t* prim, float* t) {
-    if (!desc || nq < 0 || (mode != 0 && mode != 1) || (nq > 0 && (!o || !d || !prim || !t)))
+    return sdmm_scene_intersect_host_levels(desc, 0, nq, o, d, mint, maxt, mode, prim, t);
+}
+
+int sdmm_scene_intersect_host_levels(const sdmm_scene_desc* desc, int max_levels, int64_t nq, const float* o,
+                                     const float* d, float mint, float maxt, int mode, int32_t* prim, float* t) {
+    if (!desc || max_levels < 0 || nq < 0 || (mode != 0 && mode != 1) || (nq > 0 && (!o || !d || !prim || !t)))
         return fail(SDMM_E_INVALID, "sdmm_scene_intersect_host: invalid argument (mode 0 or 1)");
     std::vector<QuadDev> qs;
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -757,7 +762,7 @@ int sdmm_scene_intersect_host(const sdmm_scene_desc* desc, int64_t nq, const flo
     if (rc) return rc;
     MeshBvh mesh;
     if (desc->n_triangles > 0) {
-        rc = prep_mesh(desc, "sdmm_scene_intersect_host", 0, &mesh);
+        rc = prep_mesh(desc, "sdmm_scene_intersect_host", max_levels, &mesh);
         if (rc) return rc;
     }
     // the device's float environment: denormals flushed (-fgpu-flush-denormals-to-zero)

@@ -1,9 +1,11 @@
 // mesh_bvh_check.cpp -- the BVH build and both traversal modes (mesh_bvh.h /
 // mesh_bvh.cpp) as a stand-alone program for a sanitizer build (tests/
-// test_mesh.py): the fixture file of the Python tests, then 20 000 random
-// triangles over repeated vertices with 10 000 rays.  Every ray's (prim, t)
-// must agree bitwise between the BVH and the loop.  Writes the fixture's hits
-// to <fixture>.out (prim[n] int32, t[n] float32).
+// test_mesh.py): the fixture files of the Python tests (the torus, and meshes
+// whose trees are as deep as the stack allows), then 20 000 random triangles
+// over repeated vertices with 10 000 rays.  Every ray's (prim, t) must agree
+// bitwise between the BVH and the loop, and with a walk over a stack that
+// checks its bounds and reports the deepest slot written.  Writes each
+// fixture's hits to <fixture>.out (prim[n] int32, t[n] float32).
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -21,8 +23,30 @@ static uint32_t rnd() {
 }
 static float uni() { return (float)(rnd() & 0xFFFFFF) * (1.0f / 16777216.0f); }
 
+// kBvhStack entries like the host's and the kernels' stacks, every access checked
+struct CheckedStack {
+    int32_t v[kBvhStack];
+    int deepest = -1;
+    bool out_of_bounds = false;
+    void push(int level, int32_t node) {
+        if (level < 0 || level >= kBvhStack) {
+            out_of_bounds = true;
+            return;
+        }
+        v[level] = node;
+        if (level > deepest) deepest = level;
+    }
+    int32_t pop(int level) {
+        if (level < 0 || level > deepest) {
+            out_of_bounds = true;
+            return 0;
+        }
+        return v[level];
+    }
+};
+
 static int run(const std::vector<float>& v, const std::vector<int32_t>& tri, const std::vector<float>& o,
-               const std::vector<float>& d, std::vector<int32_t>* prim_out, std::vector<float>* t_out) {
+               const std::vector<float>& d, float mint, std::vector<int32_t>* prim_out, std::vector<float>* t_out) {
     const int nt = (int)(tri.size() / 3);
     std::vector<int32_t> bsdf((size_t)nt, 0);
     MeshInput in;
@@ -44,13 +68,21 @@ static int run(const std::vector<float>& v, const std::vector<int32_t>& tri, con
     }
     const size_t nq = o.size() / 3;
     int hits = 0;
+    CheckedStack cs;
     for (size_t i = 0; i < nq; ++i) {
-        int best[2] = {-1, -1};
-        float tb[2] = {__builtin_inff(), __builtin_inff()};
+        int best[3] = {-1, -1, -1};
+        float tb[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
         for (int mode = 0; mode < 2; ++mode)
-            mesh_closest_host(m, 0, mode, &o[3 * i], &d[3 * i], 1e-4f, __builtin_inff(), best[mode], tb[mode]);
-        if (best[0] != best[1] || std::memcmp(&tb[0], &tb[1], sizeof(float)) != 0) {
-            std::printf("ray %zu: BVH (%d, %.9g) != loop (%d, %.9g)\n", i, best[0], tb[0], best[1], tb[1]);
+            mesh_closest_host(m, 0, mode, &o[3 * i], &d[3 * i], mint, __builtin_inff(), best[mode], tb[mode]);
+        bvh_closest(m.nodes.data(), m.tris.data(), 0, &o[3 * i], &d[3 * i], mint, __builtin_inff(), best[2], tb[2], cs);
+        if (cs.out_of_bounds) {
+            std::printf("ray %zu: the walk left the stack's %d entries\n", i, kBvhStack);
+            return 1;
+        }
+        if (best[0] != best[1] || std::memcmp(&tb[0], &tb[1], sizeof(float)) != 0 || best[0] != best[2] ||
+            std::memcmp(&tb[0], &tb[2], sizeof(float)) != 0) {
+            std::printf("ray %zu: BVH (%d, %.9g) != loop (%d, %.9g) or != the checked walk (%d, %.9g)\n", i, best[0],
+                        tb[0], best[1], tb[1], best[2], tb[2]);
             return 1;
         }
         hits += best[0] >= 0;
@@ -59,20 +91,18 @@ static int run(const std::vector<float>& v, const std::vector<int32_t>& tri, con
             t_out->push_back(tb[0]);
         }
     }
-    std::printf("%d triangles, %d levels, %zu nodes, %zu rays, %d hits\n", nt, m.levels, m.nodes.size(), nq, hits);
+    std::printf("%d triangles, %d levels, %zu nodes, %zu rays, %d hits, deepest stack slot %d\n", nt, m.levels,
+                m.nodes.size(), nq, hits, cs.deepest);
     return 0;
 }
 
-int main(int argc, char** argv) {
-    if (argc < 2) {
-        std::printf("usage: mesh_bvh_check <fixture file>\n");
-        return 2;
-    }
-    // the fixture: int32 nv, nt, nq; vertices, triangles, origins, directions
-    std::FILE* f = std::fopen(argv[1], "rb");
+// one fixture file: int32 nv, nt, nq; float mint; vertices, triangles, origins, directions
+static int run_file(const char* path) {
+    std::FILE* f = std::fopen(path, "rb");
     if (!f) return 2;
     int32_t hdr[3];
-    if (std::fread(hdr, sizeof(int32_t), 3, f) != 3) return 2;
+    float mint;
+    if (std::fread(hdr, sizeof(int32_t), 3, f) != 3 || std::fread(&mint, sizeof(float), 1, f) != 1) return 2;
     std::vector<float> v((size_t)hdr[0] * 3), o((size_t)hdr[2] * 3), d((size_t)hdr[2] * 3);
     std::vector<int32_t> tri((size_t)hdr[1] * 3);
     if (std::fread(v.data(), sizeof(float), v.size(), f) != v.size() ||
@@ -83,12 +113,22 @@ int main(int argc, char** argv) {
     std::fclose(f);
     std::vector<int32_t> prim;
     std::vector<float> t;
-    if (run(v, tri, o, d, &prim, &t)) return 1;
-    std::FILE* g = std::fopen((std::string(argv[1]) + ".out").c_str(), "wb");
+    if (run(v, tri, o, d, mint, &prim, &t)) return 1;
+    std::FILE* g = std::fopen((std::string(path) + ".out").c_str(), "wb");
     if (!g) return 2;
     std::fwrite(prim.data(), sizeof(int32_t), prim.size(), g);
     std::fwrite(t.data(), sizeof(float), t.size(), g);
     std::fclose(g);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 2) {
+        std::printf("usage: mesh_bvh_check <fixture file>...\n");
+        return 2;
+    }
+    for (int k = 1; k < argc; ++k)
+        if (const int rc = run_file(argv[k])) return rc;
 
     // 20 000 random triangles over 3 000 vertices on a coarse grid (repeated
     // positions: coincident centroids, coplanar and duplicated triangles)
@@ -126,7 +166,7 @@ int main(int argc, char** argv) {
         if (i % 50 == 0) rd[3 * i + (i / 50) % 3] = 0.0f;                 // axis-parallel components
         if (i % 125 == 0) ro[3 * i] = (float)(rnd() % 33) * 0.125f - 2.0f;   // origins on the vertex grid's planes
     }
-    if (run(rv, rt, ro, rd, nullptr, nullptr)) return 1;
+    if (run(rv, rt, ro, rd, 1e-4f, nullptr, nullptr)) return 1;
     std::printf("mesh_bvh_check ok\n");
     return 0;
 }

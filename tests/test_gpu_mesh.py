@@ -2,7 +2,11 @@
 against intersect_host bitwise, the scene AABB, a quad-only description
 unchanged by the new fields, a convex diffuse body in a furnace (exactly rho),
 the Cornell box with its cubes as triangles against the quad scene, and the
-torus scene (guided, product, brute-force A/B in a child process)."""
+torus scene (guided, product, brute-force A/B in a child process); the same
+bitwise equality on meshes of 24 inner levels, on a ladder whose rays fill the
+LDS stack, on hard rays (grazing, surface-leaving, signed zeros, non-finite),
+on shared vertices and edges, on exact ties and on small batches, and the Li
+kernels' own stack on a 24-level tree against the loop."""
 import os
 import subprocess
 import sys
@@ -360,3 +364,171 @@ def test_torus_scene(pkg, scenes, gpu, plog, K, tmp_path):
                        text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert np.array_equal(np.load(out).view(np.uint32), bvh.view(np.uint32))
+
+
+# ---- the traversal stack at full depth, edge rays ------------------------------
+def _device_equals_host(pkg, gpu, desc, o, d, mint=mf.MINT, maxts=None, sc=None):
+    """Scene.intersect mode 0 == mode 1 == intersect_host bitwise on (prim, t
+    as bits), at maxt = inf and at a finite maxt (default: the median hit
+    distance, which cuts about half the hits).  The host's two modes agree
+    first: a device difference is then the device's.  Returns the host's hits
+    at maxt = inf."""
+    sc = sc or pkg.Scene(mf.camera_fields(desc))
+    op, dp = _planes(o, gpu), _planes(d, gpu)
+    first = None
+    for maxt in (np.inf, None) if maxts is None else maxts:
+        if maxt is None:
+            maxt = float(np.median(first[1][np.isfinite(first[1])]))
+        hp, ht = pkg.intersect_host(desc, o, d, mint, maxt, 0)
+        lp, lt = pkg.intersect_host(desc, o, d, mint, maxt, 1)
+        assert np.array_equal(hp, lp) and np.array_equal(ht.view(np.uint32), lt.view(np.uint32)), maxt
+        for mode in (0, 1):
+            prim, t = _bits(*sc.intersect(op, dp, mint, float(maxt), mode))
+            bad = np.flatnonzero((prim != hp) | (t != ht.view(np.uint32)))
+            assert bad.size == 0, (mode, maxt, bad[:8], prim[bad[:8]], hp[bad[:8]])
+        first = first or (hp, ht)
+    return first
+
+
+@pytest.mark.parametrize("which,kind", [("wide", "local"), ("narrow", "local"), ("narrow", "outside"),
+                                        ("ladder", "axial")])
+def test_deep_mesh_intersect_equals_host_bitwise(pkg, gpu, which, kind):
+    """A BVH of 24 inner levels: triangles over six or four decades of size,
+    4099 rays (their stacks reach slot 13 or so), and the ladder, whose rays
+    fill the LDS stack as far as a tree of 24 levels can (slot 22), in threads
+    t and t + 128 of a workgroup at once."""
+    if which == "ladder":
+        desc, (o, d), mint = mf.ladder_desc(pkg), mf.ladder_rays(), mf.LADDER_MINT
+    else:
+        desc, (o, d), mint = mf.deep_desc(pkg, which), mf.deep_rays(which, kind), mf.MINT
+    hp, ht = _device_equals_host(pkg, gpu, desc, o, d, mint)
+    assert (hp >= 0).mean() > 0.9
+
+
+def test_deep_mesh_batch_sizes(pkg, gpu):
+    """Batches smaller than a wave, of one workgroup less and more a ray, and
+    with a ragged last block: each ray's answer is its answer in the full batch."""
+    desc = mf.deep_desc(pkg, "wide")
+    o, d = mf.deep_rays("wide", "local")
+    sc = pkg.Scene(mf.camera_fields(desc))
+    hp, ht = pkg.intersect_host(desc, o, d, mf.MINT, np.inf, 0)
+    for n in (1, 63, 255, 256, 257, 4099):
+        # (from the end: the batch of 1 is not the full batch's lane 0)
+        oo, dd = o[len(o) - n:], d[len(o) - n:]
+        for mode in (0, 1):
+            prim, t = _bits(*sc.intersect(_planes(oo, gpu), _planes(dd, gpu), mf.MINT, float("inf"), mode))
+            assert prim.shape == (n,)
+            assert np.array_equal(prim, hp[len(o) - n:]) and np.array_equal(t, ht[len(o) - n:].view(np.uint32)), (n, mode)
+
+
+@pytest.mark.parametrize("mint", [1e-4, 1e-3])
+def test_hard_rays_intersect_equals_host_bitwise(pkg, scenes, gpu, mint):
+    """Grazing rays, rays leaving the surface, -0.0 components, the zero
+    direction and non-finite rays among ordinary ones in the same wave."""
+    o, d, kinds = mf.hard_rays(scenes)
+    hp, ht = _device_equals_host(pkg, gpu, mf.torus_desc(scenes), o, d, mint)
+    assert np.all(hp[kinds["special"]] == -1) and np.all(np.isposinf(ht[kinds["special"]]))
+
+
+def test_flat_grid_and_tie_intersect_equals_host_bitwise(pkg, gpu):
+    """Rays through shared vertices and edges (the lowest id), rays in the
+    plane (nothing), and a quad against a coplanar triangle at exactly the
+    same t (the quad); maxt == t excludes the hit."""
+    v, tr = mf.flat_grid()
+    desc = mf.base_desc(v, tr, quads=False)
+    o, d, expected = mf.flat_grid_rays()
+    oi, di = mf.flat_grid_inplane_rays()
+    hp, ht = _device_equals_host(pkg, gpu, desc, np.concatenate([o, oi]), np.concatenate([d, di]),
+                                 maxts=(np.inf, 1.0, float(np.nextafter(np.float32(1), np.float32(2)))))
+    assert np.array_equal(hp[:len(o)], expected) and np.all(ht[:len(o)] == np.float32(1))
+    assert np.all(hp[len(o):] == -1)
+    o, d, expected = mf.tie_rays()
+    hp, ht = _device_equals_host(pkg, gpu, mf.tie_desc(), o, d,
+                                 maxts=(np.inf, 1.0, float(np.nextafter(np.float32(1), np.float32(2)))))
+    assert np.array_equal(hp, expected)
+
+
+FURNACE_SPIRAL = (8192, 1e-2, 1e2, 2)      # (the seed: 24 inner levels with the box's 12 triangles; asserted)
+
+
+def _deep_furnace(scenes):
+    """The closed box of emitter triangles of _triangle_furnace round
+    spiral_mesh(8192, 1e-2, 1e2) scaled by 0.02 (diffuse, rho 0.6): the Li
+    kernels walk a BVH of 24 inner levels."""
+    d = _triangle_furnace(scenes, body=False)
+    bv, bt, _ = mf.spiral_mesh(*FURNACE_SPIRAL)
+    bv = bv * np.float32(0.02)
+    v = d["mesh_vertices"].reshape(-1, 3)
+    nb = len(d["tri_bsdf"])
+    d.update(mesh_vertices=np.concatenate([v, bv]).reshape(-1),
+             triangles=np.concatenate([d["triangles"].reshape(-1, 3), bt + len(v)]).reshape(-1),
+             tri_bsdf=np.concatenate([d["tri_bsdf"], np.ones(len(bt), np.int32)]),
+             tri_emitter=np.concatenate([d["tri_emitter"], np.full(len(bt), -1, np.int32)]),
+             tri_flip_normals=np.concatenate([d["tri_flip_normals"], np.zeros(len(bt), np.int32)]))
+    assert nb == 12
+    return d
+
+
+_DEEP_CHILD = """
+import sys
+import numpy as np
+sys.path.insert(0, {root!r})
+sys.path.insert(0, {tests!r})
+from conftest import load_pkg
+import importlib
+pkg = load_pkg()
+scenes = importlib.import_module("sdmm_mitsuba_amd.scenes")
+from test_gpu_li import _tree
+import test_gpu_mesh as tg
+sc = pkg.Scene(tg._deep_furnace(scenes))
+img = sc.render(_tree(pkg, sc), None, spp=8, guided=False, seed=4343)[0]
+np.save({out!r}, img.cpu().numpy())
+"""
+
+
+def test_li_kernels_walk_a_deep_bvh(pkg, scenes, gpu, tmp_path, monkeypatch):
+    """The camera and shade kernels' own LDS stack at 24 inner levels: the
+    image through the BVH is bitwise the image of the brute-force loop
+    (SDMM_MESH_BRUTE=1, read at scene creation) -- unguided against a fresh
+    child process, and one guided pass (the MESH shade kernels with guiding)
+    against a loop scene created in this process with the same tree and
+    mixtures."""
+    import torch
+    monkeypatch.delenv("SDMM_MESH_BRUTE", raising=False)
+    desc = _deep_furnace(scenes)
+    assert pkg.mesh_bvh_dump(desc)["levels"] == 24
+    # the host's walk and loop agree on the camera rays: a difference below is not the scale envelope's
+    o, d = _camera_rays(desc)
+    hp, ht = pkg.intersect_host(desc, o, d, 1e-2, np.inf, 0)
+    lp, lt = pkg.intersect_host(desc, o, d, 1e-2, np.inf, 1)
+    assert np.array_equal(hp, lp) and np.array_equal(ht.view(np.uint32), lt.view(np.uint32))
+    assert hp.min() >= 0 and len(np.unique(hp[hp >= 12])) > 50                   # the closed box; many of the body's triangles
+    sc = pkg.Scene(desc)
+    prim, t = _bits(*sc.intersect(_planes(o, gpu), _planes(d, gpu), 1e-2, float("inf"), 0))
+    assert np.array_equal(prim, hp) and np.array_equal(t, ht.view(np.uint32))
+    tree = _tree(pkg, sc)
+    walk = sc.render(tree, None, spp=8, guided=False, seed=4343)[0].cpu().numpy()
+    assert np.isfinite(walk).all() and 0.0 < walk.mean() < 1.0
+    out = tmp_path / "brute.npy"
+    script = tmp_path / "brute_child.py"
+    script.write_text(_DEEP_CHILD.format(root=str(ROOT), tests=str(ROOT / "tests"), out=str(out)))
+    r = subprocess.run([sys.executable, str(script)], env={**os.environ, "SDMM_MESH_BRUTE": "1"}, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    loop = np.load(out)
+    differ = np.flatnonzero((loop.view(np.uint32) != walk.view(np.uint32)).any(0).reshape(-1))
+    assert differ.size == 0, f"{differ.size} pixels differ between the walk and the loop, first {differ[:8]}"
+    # guided: the same tree and mixtures on a walk scene and a loop scene
+    node_mix = _train(pkg, sc, tree, 4, 8, K=16)
+    assert any(m is not None for m in node_mix)
+    gw, _, st = sc.render(tree, node_mix, spp=8, guided=True, seed=4344)
+    gw = gw.clone()
+    assert st["guided_queries"] > 0
+    monkeypatch.setenv("SDMM_MESH_BRUTE", "1")
+    brute_sc = pkg.Scene(desc)
+    monkeypatch.delenv("SDMM_MESH_BRUTE")
+    gl, _, sl = brute_sc.render(tree, node_mix, spp=8, guided=True, seed=4344)
+    assert torch.equal(gw, gl) and st == sl
+    # (the loop scene is the loop: its unguided image is the child's)
+    again = brute_sc.render(tree, None, spp=8, guided=False, seed=4343)[0].cpu().numpy()
+    assert np.array_equal(again.view(np.uint32), loop.view(np.uint32))

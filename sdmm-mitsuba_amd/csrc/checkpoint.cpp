@@ -27,10 +27,7 @@
 #include <vector>
 
 #include "../../include/sdmm_gpu.h"
-
-namespace sdmm_detail {
-int set_error(int code, const char* msg);   // sdmm_api.cpp
-}
+#include "host_xfer.h"
 
 namespace {
 

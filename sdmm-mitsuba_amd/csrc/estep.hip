@@ -28,6 +28,7 @@
 //     group writes one contiguous K*4-byte row per sample (CPL*4 B per lane,
 //     non-temporal vector stores).
 #include "sdmm_device.h"
+#include "launch.h"
 
 #include <cstdlib>
 
@@ -1388,60 +1389,36 @@ hipError_t launch_estep_resp(int cpl, int lps, const float* ep, int Kp, int K, c
 }
 
 // Tiled responsibility kernel (64 < K <= 128, Kp == 128): chunk is a multiple
-// of 64 samples per wave.
-// Variants (SDMM_RESP_VARIANT): {SB, KT, waves per SIMD}.
-#define SDMM_TILE_VARIANTS(X) X(0, 2, 16, 4) X(1, 2, 8, 4) X(2, 2, 16, 3) X(3, 4, 16, 3) X(4, 2, 8, 3)
-
-hipError_t launch_estep_resp_tile(int variant, const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
+// of 64 samples per wave.  One configuration: SB = 2, KT = 8, 3 waves per SIMD.
+hipError_t launch_estep_resp_tile(const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
                                   int64_t chunk, float* resp, hipStream_t st) {
     if (Kp != 128 || K <= 64 || K > 128) return hipErrorInvalidValue;
     constexpr int wpb = 4;
     const int64_t waves = (n + chunk - 1) / chunk;
     const int64_t blocks = (waves + wpb - 1) / wpb;
-#define X(V, SB, KT, OCC)                                                                           \
-    if (variant == V) {                                                                            \
-        hipLaunchKernelGGL((estep_resp_tile_kernel<wpb, SB, KT, OCC>), dim3((unsigned)blocks), dim3(64 * wpb), 0, \
-                           st, ep, Kp, K, s, n, chunk, resp);                                     \
-        return hipGetLastError();                                                                  \
-    }
-    SDMM_TILE_VARIANTS(X)
-#undef X
-    return hipErrorInvalidValue;
+    hipLaunchKernelGGL((estep_resp_tile_kernel<wpb, 2, 8, 3>), dim3((unsigned)blocks), dim3(64 * wpb), 0, st, ep, Kp,
+                       K, s, n, chunk, resp);
+    return hipGetLastError();
 }
 
-hipError_t estep_resp_tile_occupancy(int variant, int* blocks_per_cu) {
-#define X(V, SB, KT, OCC)                                                                           \
-    if (variant == V)                                                                              \
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(                                       \
-            blocks_per_cu, reinterpret_cast<const void*>(&estep_resp_tile_kernel<4, SB, KT, OCC>), 256, 0);
-    SDMM_TILE_VARIANTS(X)
-#undef X
-    return hipErrorInvalidValue;
+hipError_t estep_resp_tile_occupancy(int* blocks_per_cu) {
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        blocks_per_cu, reinterpret_cast<const void*>(&estep_resp_tile_kernel<4, 2, 8, 3>), 256, 0);
 }
 
-const char* estep_resp_tile_name(int variant) {
-#define X(V, SB, KT, OCC) \
-    if (variant == V) return "estep_resp_tile_kernel<4," #SB "," #KT "," #OCC ">";
-    SDMM_TILE_VARIANTS(X)
-#undef X
-    return "estep_resp_tile_kernel<?>";
-}
+const char* estep_resp_tile_name() { return "estep_resp_tile_kernel<4,2,8,3>"; }
 
 // Tiled statistics kernel (64 < K <= 128, Kp == 128): `blocks` workgroups of 4
 // waves, chunk a multiple of 64 samples per wave; one partial row per block.
-hipError_t launch_estep_stats_tile(int variant, const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
+hipError_t launch_estep_stats_tile(const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
                                    int64_t chunk, int blocks, float* partials, int pstride, hipStream_t st,
                                    const LeafDesc* leaves, const int2* items) {
     // one row slot per wave (GROUP: one shared slot)
     const size_t row = sizeof(float) * (size_t)(ST_FIELDS * Kp + 2);
     const size_t lds = (Kp == 128) ? 4 * row : row;
     if (Kp == 128 && K > 64 && K <= 128) {
-        if (variant == 1)
-            hipLaunchKernelGGL((estep_stats_tile_kernel<4, 3>), dim3(blocks), dim3(256), lds, st, ep, Kp, K, s, n,
-                               chunk, partials, pstride, leaves, items);
-        else
-            hipLaunchKernelGGL((estep_stats_tile_kernel<4, 2>), dim3(blocks), dim3(256), lds, st, ep, Kp, K, s, n,
-                               chunk, partials, pstride, leaves, items);
+        hipLaunchKernelGGL((estep_stats_tile_kernel<4, 2>), dim3(blocks), dim3(256), lds, st, ep, Kp, K, s, n,
+                           chunk, partials, pstride, leaves, items);
     } else if (Kp == 256 && K > 128 && K <= 256) {
         hipLaunchKernelGGL((estep_stats_tile_kernel<2, 2, true>), dim3(blocks), dim3(128), lds, st, ep, Kp, K, s, n,
                            chunk, partials, pstride, leaves, items);
@@ -1454,7 +1431,7 @@ hipError_t launch_estep_stats_tile(int variant, const float* ep, int Kp, int K, 
     return hipGetLastError();
 }
 // resident workgroups per CU; *waves_per_wg: the waves of one (GROUP: one chunk)
-hipError_t estep_stats_tile_occupancy(int variant, int Kp, int* blocks_per_cu) {
+hipError_t estep_stats_tile_occupancy(int Kp, int* blocks_per_cu) {
     const size_t row = sizeof(float) * (size_t)(ST_FIELDS * Kp + 2);
     const size_t lds = (Kp == 128) ? 4 * row : row;
     if (Kp == 256)
@@ -1463,9 +1440,8 @@ hipError_t estep_stats_tile_occupancy(int variant, int Kp, int* blocks_per_cu) {
     if (Kp == 512)
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(
             blocks_per_cu, reinterpret_cast<const void*>(&estep_stats_tile_kernel<4, 2, true>), 256, lds);
-    const void* f = variant == 1 ? reinterpret_cast<const void*>(&estep_stats_tile_kernel<4, 3>)
-                                 : reinterpret_cast<const void*>(&estep_stats_tile_kernel<4, 2>);
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, 256, lds);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        blocks_per_cu, reinterpret_cast<const void*>(&estep_stats_tile_kernel<4, 2>), 256, lds);
 }
 
 hipError_t launch_estep_stats(int cpl, int lps, const float* ep, int Kp, int K, const SamplesDev& s,

@@ -34,6 +34,7 @@
 // lane (row group sg, col) writes component 16 r + col of rows 4 sg + j, i.e.
 // every store instruction writes four 64-byte row segments.
 #include "sdmm_device.h"
+#include "launch.h"
 
 namespace sdmm {
 
@@ -274,28 +275,17 @@ estep_resp_mfma_kernel(const float* __restrict__ ep, int Kp, int K, SamplesDev s
 }
 
 // ---------------------------------------------------------------------------
-// Rounds R = Kp / 16 and the register budget (waves per SIMD) of each: the
-// default budget per R, and variant v (SDMM_RESP_VARIANT) 1..3 = 2, 3, 4 waves.
-#define SDMM_MFMA_CONFIGS(X) \
-    X(1, 4) X(2, 4) X(4, 4) X(8, 2) X(8, 3) X(8, 4) X(16, 2) X(16, 3) X(32, 2)
+// Rounds R = Kp / 16 and the register budget (waves per SIMD) of each.
+#define SDMM_MFMA_CONFIGS(X) X(1, 4) X(2, 4) X(4, 4) X(8, 3) X(16, 2) X(32, 2)
 
-static int mfma_occ(int R, int variant) {
-    if (variant >= 1 && variant <= 3) {
-        const int o = variant + 1;
-        if ((R == 8) || (R == 16 && o <= 3)) return o;
-    }
-    return R <= 4 ? 4 : (R == 8 ? 3 : 2);
-}
-
-hipError_t launch_estep_resp_mfma(int variant, const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
+hipError_t launch_estep_resp_mfma(const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
                                   int64_t chunk, float* resp, hipStream_t st) {
     if (Kp % 16 != 0 || K > Kp || chunk % 16 != 0) return hipErrorInvalidValue;
     const int R = Kp / 16;
-    const int occ = mfma_occ(R, variant);
     const int64_t waves = (n + chunk - 1) / chunk;
     const int64_t blocks = (waves + 3) / 4;
 #define X(RR, OO)                                                                                      \
-    if (R == RR && occ == OO) {                                                                        \
+    if (R == RR) {                                                                                     \
         hipLaunchKernelGGL((estep_resp_mfma_kernel<RR, OO>), dim3((unsigned)blocks), dim3(256), 0, st, ep, Kp, K, \
                            s, n, chunk, resp);                                                         \
         return hipGetLastError();                                                                      \
@@ -305,11 +295,10 @@ hipError_t launch_estep_resp_mfma(int variant, const float* ep, int Kp, int K, c
     return hipErrorInvalidValue;
 }
 
-hipError_t estep_resp_mfma_occupancy(int variant, int Kp, int* blocks_per_cu) {
+hipError_t estep_resp_mfma_occupancy(int Kp, int* blocks_per_cu) {
     const int R = Kp / 16;
-    const int occ = mfma_occ(R, variant);
 #define X(RR, OO)                                                                                      \
-    if (R == RR && occ == OO)                                                                          \
+    if (R == RR)                                                                                       \
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(                                           \
             blocks_per_cu, reinterpret_cast<const void*>(&estep_resp_mfma_kernel<RR, OO>), 256, 0);
     SDMM_MFMA_CONFIGS(X)
@@ -317,10 +306,12 @@ hipError_t estep_resp_mfma_occupancy(int variant, int Kp, int* blocks_per_cu) {
     return hipErrorInvalidValue;
 }
 
-const char* estep_resp_mfma_name(int variant, int Kp) {
-    static thread_local char buf[64];
-    snprintf(buf, sizeof buf, "estep_resp_mfma_kernel<%d,%d>", Kp / 16, mfma_occ(Kp / 16, variant));
-    return buf;
+const char* estep_resp_mfma_name(int Kp) {
+#define X(RR, OO) \
+    if (Kp / 16 == RR) return "estep_resp_mfma_kernel<" #RR "," #OO ">";
+    SDMM_MFMA_CONFIGS(X)
+#undef X
+    return "estep_resp_mfma_kernel<?>";
 }
 
 }  // namespace sdmm

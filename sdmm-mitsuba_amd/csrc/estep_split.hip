@@ -49,6 +49,7 @@
 // At R = 8 the default is the band form further down (resp_band_body): the
 // image stays in registers, a wave owning 32 components instead of 16 samples.
 #include "sdmm_device.h"
+#include "launch.h"
 
 namespace sdmm {
 
@@ -1088,22 +1089,21 @@ estep_resp_split_band_inline_kernel(const float* __restrict__ ep, int Kp, int K,
 #define SDMM_SPLIT_CONFIGS(X) X(1, 4, 4) X(2, 4, 4) X(4, 4, 4) X(8, SDMM_SPLIT_R8_WPB, SDMM_SPLIT_R8_OCC)
 
 // R = 8 (K = 128): the band form (resp_band_body: 4-wave workgroups, three per
-// CU, the coefficient image in registers) unless the variant asks for the LDS
-// image (kSplitLdsVariant, SDMM_RESP_KERNEL=splitlds: the A/B and comparison
+// CU, the coefficient image in registers) unless the caller asks for the LDS
+// image (lds_image, SDMM_RESP_KERNEL=splitlds: the A/B and comparison
 // configuration), which is one 12-wave workgroup per CU at 3 waves per SIMD
 // (the 64-KB coefficient image, the 48 KB of half-row stages and the 18 KB of
 // feature rings share the LDS).  Round 4 measured 4-wave / 2-per-SIMD and
 // 8-wave / 2-per-SIMD workgroups of that form slower.
-constexpr int kSplitLdsVariant = 15;
-static bool split_band(int R, int variant) { return R == 8 && variant != kSplitLdsVariant; }
-static void split_cfg(int R, int variant, int* wpb, int* occ) {
+static bool split_band(int R, bool lds_image) { return R == 8 && !lds_image; }
+static void split_cfg(int R, bool lds_image, int* wpb, int* occ) {
     *wpb = 4;
     *occ = 4;
     if (R == 8) {
         *wpb = SDMM_SPLIT_R8_WPB;
         *occ = SDMM_SPLIT_R8_OCC;
     }
-    if (split_band(R, variant)) {
+    if (split_band(R, lds_image)) {
         *wpb = kBandWaves;
         *occ = kBandOcc;
     }
@@ -1127,18 +1127,18 @@ hipError_t launch_estep_resp_image(const float* ep, int Kp, void* img, hipStream
 // is one round of them, fewer when n has fewer tiles).  img: the prebuilt
 // coefficient image of ep (launch_estep_resp_image), or NULL for the kernel
 // that builds it in every workgroup.
-hipError_t launch_estep_resp_split(int variant, const float* ep, const void* img, int Kp, int K, const SamplesDev& s,
+hipError_t launch_estep_resp_split(bool lds_image, const float* ep, const void* img, int Kp, int K, const SamplesDev& s,
                                    int64_t n, int64_t resident_waves, float* resp, hipStream_t st) {
     if (!estep_resp_split_supported(Kp) || K > Kp || resident_waves <= 0) return hipErrorInvalidValue;
     const int R = Kp / 16;
     int wpb, occ;
-    split_cfg(R, variant, &wpb, &occ);
+    split_cfg(R, lds_image, &wpb, &occ);
     const int64_t tiles = (n + 15) / 16;
     const int64_t blocks = ((tiles < resident_waves ? tiles : resident_waves) + wpb - 1) / wpb;
     const int64_t waves = blocks * wpb;
     // the kernel steps its addresses by 16 waves samples held in 32 bits
     if (waves >= (int64_t)1 << 26) return hipErrorInvalidValue;
-    if (split_band(R, variant)) {
+    if (split_band(R, lds_image)) {
         // one round of resident workgroups, fewer when n has fewer super-tiles
         const int64_t sup = (n + 63) / 64, res = resident_waves / kBandWaves > 0 ? resident_waves / kBandWaves : 1;
         const unsigned grid = (unsigned)(sup < res ? sup : res);
@@ -1166,12 +1166,12 @@ hipError_t launch_estep_resp_split(int variant, const float* ep, const void* img
 }
 
 // resident waves per CU of the configuration
-hipError_t estep_resp_split_occupancy(int variant, int Kp, bool inline_image, int* waves_per_cu) {
+hipError_t estep_resp_split_occupancy(bool lds_image, int Kp, bool inline_image, int* waves_per_cu) {
     const int R = Kp / 16;
     int wpb, occ;
-    split_cfg(R, variant, &wpb, &occ);
+    split_cfg(R, lds_image, &wpb, &occ);
     int blocks = 0;
-    if (split_band(R, variant)) {
+    if (split_band(R, lds_image)) {
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
             &blocks,
             inline_image ? reinterpret_cast<const void*>(&estep_resp_split_band_inline_kernel<8, kBandWaves, kBandOcc>)
@@ -1195,11 +1195,11 @@ hipError_t estep_resp_split_occupancy(int variant, int Kp, bool inline_image, in
     return hipErrorInvalidValue;
 }
 
-const char* estep_resp_split_name(int variant, int Kp, bool inline_image) {
+const char* estep_resp_split_name(bool lds_image, int Kp, bool inline_image) {
     static thread_local char buf[64];
     int wpb, occ;
-    split_cfg(Kp / 16, variant, &wpb, &occ);
-    snprintf(buf, sizeof buf, "estep_resp_split%s%s_kernel<%d,%d,%d>", split_band(Kp / 16, variant) ? "_band" : "",
+    split_cfg(Kp / 16, lds_image, &wpb, &occ);
+    snprintf(buf, sizeof buf, "estep_resp_split%s%s_kernel<%d,%d,%d>", split_band(Kp / 16, lds_image) ? "_band" : "",
              inline_image ? "_inline" : "", Kp / 16, wpb, occ);
     return buf;
 }

@@ -25,6 +25,7 @@
 // direction and the mixture pdf (tolerances 1e-5 / 1e-4) use the float
 // transcendentals.
 #include "sdmm_device.h"
+#include "launch.h"
 #include <cstdlib>
 
 #include <hipcub/hipcub.hpp>
@@ -354,10 +355,7 @@ __device__ __forceinline__ QueryOut finish_query(const float* gp, int Kp, const 
 // the list overflows, or the list runs out before the cutoff (only possible
 // when invalid conditionals zero out kept weights).  With K = 128 the list
 // holds a median of ~10 and a 99th percentile of ~34 entries.
-#ifndef SDMM_GUIDE_CAP_MAX
-#define SDMM_GUIDE_CAP_MAX 64
-#endif
-constexpr int kGuideCap = SDMM_GUIDE_CAP_MAX;
+constexpr int kGuideCap = kGuideCapMax;   // launch.h
 // lists of at least this capacity are built in registers (build_candidates_reg)
 constexpr int kGuideRegCap = 40;
 
@@ -556,13 +554,7 @@ struct GuideIO {
     const uint8_t* pmode;
 };
 
-// One mixture's guide record as the wavefront kernels see it (per tree node;
-// K = 0: the node has no trained mixture -> BSDF only, sdmm_proc.cpp:316-323).
-struct GuideMix {
-    const float* gp;
-    int Kp, K;
-};
-static_assert(sizeof(GuideMix) == 16, "GuideMix");
+// (GuideMix, one mixture's guide record per tree node: sdmm_device.h)
 // A mixture record known wave-uniform (a uniform-leaf wave): its fields moved
 // to SGPRs, so that the record loads of a uniform component index compile to
 // scalar loads (the compiler cannot see the uniformity through the table
@@ -3011,11 +3003,11 @@ hipError_t launch_guide(const float* gp, int Kp, int K, int64_t nq, const float*
     return hipGetLastError();
 }
 
-// The tree wavefront: every query against its own node's mixture (tab, one
+// The tree wavefront: every query against its own node's mixture (tb, one
 // GuideMix per tree node; kmax = the largest K in it).  Same two-pass shape
 // and the same per-query arithmetic as launch_guide.  sort: always used
 // (Morton order keeps a wave inside one leaf) unless null.
-hipError_t launch_guide_tree(const void* nodes, const void* tab, int kmax, int64_t nq, const float* const c[3],
+hipError_t launch_guide_tree(const STNodeDev* nd, const GuideMix* tb, int kmax, int64_t nq, const float* const c[3],
                              const float* const u[3], const float* const dgiven[3], float* const d[3],
                              float* pdf, int32_t* comp, int32_t* node_out, float norm2, float norm3, int cap,
                              int* fb_count, int32_t* fb_list, int cus, hipStream_t st,
@@ -3031,7 +3023,6 @@ hipError_t launch_guide_tree(const void* nodes, const void* tab, int kmax, int64
     GuideConsts gc{norm2, norm3};
     hipError_t e = hipMemsetAsync(fb_count, 0, sizeof(int), st);
     if (e != hipSuccess) return e;
-    const STNodeDev* nd = (const STNodeDev*)nodes;
     const int32_t* perm = nullptr;
     const uint32_t* skeys = nullptr;   // leaf-major sorted keys (node in the high bits)
     int mb = 0;
@@ -3047,7 +3038,6 @@ hipError_t launch_guide_tree(const void* nodes, const void* tab, int kmax, int64
         if (e != hipSuccess) return e;
         perm = sort->idx[1];
     }
-    const GuideMix* tb = (const GuideMix*)tab;
     const dim3 grid((unsigned)((nq + T - 1) / T));
     const int fb_blocks = cus * 16;
     const GuideIO io = make_io(c, u, dgiven, d, pdf, comp, pmode);
@@ -3205,17 +3195,17 @@ hipError_t launch_guide_product(const float* gp, int Kp, int K, const float* con
     return hipGetLastError();
 }
 
-// The product wavefront over the tree (tab / cctab per node, kmax the largest
+// The product wavefront over the tree (tb / cc per node, kmax the largest
 // K): candidate pass, then the full-K queries one per wave.  Modes: sampling
 // (dgiven null), pdf only (dgiven, no choice), mixed (dgiven + choice: a pdf
 // query where choice <= the query's h).
-hipError_t launch_guide_product_tree(const void* nodes, const void* tab, const void* cctab, int kmax, int64_t nq,
-                                     const float* const c[3], const float* const u[3], const float* choice,
-                                     const float* const dgiven[3], float* const d[3], float* pdf, int32_t* comp,
-                                     int32_t* node_out, const int32_t* material, const float* const frame[9],
-                                     float* h, const float* bw, const float* bmean, const float* bcov,
-                                     const uint8_t* diffuse, int B, int M, float norm2, float norm3, int cap,
-                                     int* fb_count, int32_t* fb_list, int cus, hipStream_t st,
+hipError_t launch_guide_product_tree(const STNodeDev* nd, const GuideMix* tb, const float* const* cc, int kmax,
+                                     int64_t nq, const float* const c[3], const float* const u[3],
+                                     const float* choice, const float* const dgiven[3], float* const d[3], float* pdf,
+                                     int32_t* comp, int32_t* node_out, const int32_t* material,
+                                     const float* const frame[9], float* h, const float* bw, const float* bmean,
+                                     const float* bcov, const uint8_t* diffuse, int B, int M, float norm2, float norm3,
+                                     int cap, int* fb_count, int32_t* fb_list, int cus, hipStream_t st,
                                      const GuideSortScratch* sort, ProductScratch* scratch, int nn) {
     if (nq <= 0) return hipSuccess;
     if (nq > INT32_MAX) return hipErrorInvalidValue;
@@ -3246,7 +3236,6 @@ hipError_t launch_guide_product_tree(const void* nodes, const void* tab, const v
     const BsdfTab bt{bw, bmean, bcov, B, M, diffuse};
     hipError_t e = hipMemsetAsync(fb_count, 0, sizeof(int), st);
     if (e != hipSuccess) return e;
-    const STNodeDev* nd = (const STNodeDev*)nodes;
     const int32_t* perm = nullptr;
     const uint32_t* skeys = nullptr;   // leaf-major sorted keys (see launch_guide_tree)
     int mb = 0;
@@ -3262,8 +3251,6 @@ hipError_t launch_guide_product_tree(const void* nodes, const void* tab, const v
         if (e != hipSuccess) return e;
         perm = sort->idx[1];
     }
-    const GuideMix* tb = (const GuideMix*)tab;
-    const float* const* cc = (const float* const*)cctab;
     const dim3 grid((unsigned)((nq + 63) / 64));
     const unsigned fblocks = (unsigned)(cus * 4 * kProductWpe);
     float* pscratch = nullptr;

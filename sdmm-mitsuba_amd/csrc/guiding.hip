@@ -38,14 +38,7 @@
 #include <vector>
 
 #include "../../include/sdmm_gpu.h"
-
-namespace sdmm_detail {
-int set_error(int code, const char* msg);
-int push_training_ex(sdmm_stree* t, const sdmm_path_vertices* v, int saved_per_path, uint64_t seed,
-                     const sdmm_training_out* out, int64_t* n_out, int64_t* seg, int64_t* lost, bool reuse_counts,
-                     int64_t known_count);
-void destroy_many(sdmm_mix* const* ms, int n);
-}  // namespace sdmm_detail
+#include "host_xfer.h"
 
 namespace {
 

@@ -31,10 +31,6 @@
 
 #pragma clang fp contract(off)
 
-namespace sdmm_detail {
-int set_error(int code, const char* msg);
-}  // namespace sdmm_detail
-
 namespace {
 
 constexpr int KB = 1024;        // lanes per leaf

@@ -11,6 +11,7 @@
 // "accurate" oracle mode), component parameters rounded to float at the end.
 // FMA contraction is off so the fp64 op order equals oracle/sdmm_oracle.c's.
 #include "sdmm_device.h"
+#include "launch.h"
 
 #pragma clang fp contract(off)
 
@@ -799,11 +800,7 @@ __global__ void init_state_kernel(int K, InitScalars a, float eps, double* __res
 // covs (25K f32), bPriors (25K f32), bDepth (9K f32) from a device staging
 // block and runs set_all (MVTN::set per component on the fp64-widened mean
 // and covariance, CDF, packing).
-struct InitDesc {
-    CanonDev C;
-    float *ep, *gp, *bp, *bd;
-    double *tmean, *tcov;
-};
+// (InitDesc: sdmm_device.h)
 __global__ void __launch_bounds__(512)
 set_all_batched_kernel(int K, int Kp, const InitDesc* __restrict__ tab, const char* __restrict__ staging, size_t per,
                        float norm5) {
@@ -949,20 +946,20 @@ hemi_gen_batched_kernel(int K, HemiGenArgs a, char* __restrict__ staging, size_t
 }
 
 hipError_t launch_hemi_gen_batched(int n, int K, const float* pos, const float* nrm, const float* dist,
-                                   const uint64_t* seed, int skip, float depth_prior, void* staging, size_t per,
+                                   const uint64_t* seed, int skip, float depth_prior, char* staging, size_t per,
                                    hipStream_t st) {
     const HemiGenArgs a{pos, nrm, dist, seed, skip, depth_prior};
     const int threads = K < 64 ? 64 : (K > 256 ? 256 : K);
     hipLaunchKernelGGL(hemi_gen_batched_kernel, dim3((unsigned)n), dim3(threads), sizeof(float) * 10 * (size_t)(K / 8),
-                       st, K, a, (char*)staging, per);
+                       st, K, a, staging, per);
     return hipGetLastError();
 }
 
-hipError_t launch_set_all_batched(int n, int K, int Kp, const void* tab, const void* staging, size_t per, float norm5,
-                                  hipStream_t st) {
+hipError_t launch_set_all_batched(int n, int K, int Kp, const InitDesc* tab, const char* staging, size_t per,
+                                  float norm5, hipStream_t st) {
     const int threads = Kp < 64 ? 64 : (Kp > 512 ? 512 : Kp);
-    hipLaunchKernelGGL(set_all_batched_kernel, dim3((unsigned)n), dim3(threads), 0, st, K, Kp, (const InitDesc*)tab,
-                       (const char*)staging, per, norm5);
+    hipLaunchKernelGGL(set_all_batched_kernel, dim3((unsigned)n), dim3(threads), 0, st, K, Kp, tab, staging, per,
+                       norm5);
     return hipGetLastError();
 }
 
@@ -979,15 +976,13 @@ __global__ void gather_f64_kernel(const double* const* __restrict__ src, int n, 
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = *src[i];
 }
-hipError_t launch_gather_f64(const void* src_tab, int n, double* out, hipStream_t st) {
-    hipLaunchKernelGGL(gather_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                       (const double* const*)src_tab, n, out);
+hipError_t launch_gather_f64(const double* const* src_tab, int n, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(gather_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src_tab, n, out);
     return hipGetLastError();
 }
 
-hipError_t launch_copy_many(int n, const void* src_tab, const void* dst_tab, size_t bytes, hipStream_t st) {
-    hipLaunchKernelGGL(copy_many_kernel, dim3((unsigned)n), dim3(256), 0, st, (const uint4* const*)src_tab,
-                       (uint4* const*)dst_tab, bytes / 16);
+hipError_t launch_copy_many(int n, const uint4* const* src_tab, uint4* const* dst_tab, size_t bytes, hipStream_t st) {
+    hipLaunchKernelGGL(copy_many_kernel, dim3((unsigned)n), dim3(256), 0, st, src_tab, dst_tab, bytes / 16);
     return hipGetLastError();
 }
 

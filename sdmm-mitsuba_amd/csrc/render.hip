@@ -38,6 +38,7 @@
 // the reference's Mitsuba sampler itself is not reproducible here.
 #include "sdmm_device.h"
 #include "render_device.h"
+#include "render_launch.h"
 #include "learned_bsdf.h"
 #include "bsdf_phong.h"
 #include "bsdf_beckmann.h"
@@ -1124,23 +1125,23 @@ size_t produce_temp_bytes(int64_t n_paths, int64_t n_records, int key_bits) {
 }
 
 // count + scan: offsets[p] (n_paths + 1 entries; offsets[n_paths] = total)
-hipError_t launch_produce_count(const void* nodes, const PathsDev& P, int64_t path0, int saved, uint64_t seed,
+hipError_t launch_produce_count(const STNodeDev* nodes, const PathsDev& P, int64_t path0, int saved, uint64_t seed,
                                 int64_t* count, int64_t* offsets, void* temp, size_t temp_bytes, hipStream_t st) {
-    hipLaunchKernelGGL(produce_count_kernel, grid_for(P.P), dim3(256), 0, st, (const STNodeDev*)nodes, P, path0,
-                       saved, seed, count);
+    hipLaunchKernelGGL(produce_count_kernel, grid_for(P.P), dim3(256), 0, st, nodes, P, path0, saved, seed,
+                       count);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, count, offsets, (int)P.P + 1, st);
 }
 
-hipError_t launch_produce_records(const void* nodes, int num_nodes, int key_bits, const PathsDev& P, int64_t path0,
-                                  int saved, uint64_t seed, const int64_t* offsets, int64_t n_rec, uint32_t* keys0,
-                                  uint32_t* keys1, int64_t* codes0, int64_t* codes1, void* recs, void* temp,
-                                  size_t temp_bytes, int64_t* seg_dev, int* lost, float* const x[6],
+hipError_t launch_produce_records(const STNodeDev* nodes, int num_nodes, int key_bits, const PathsDev& P,
+                                  int64_t path0, int saved, uint64_t seed, const int64_t* offsets, int64_t n_rec,
+                                  uint32_t* keys0, uint32_t* keys1, int64_t* codes0, int64_t* codes1, void* recs,
+                                  void* temp, size_t temp_bytes, int64_t* seg_dev, int* lost, float* const x[6],
                                   float* const nrm[3], float* w, uint8_t* stats, int32_t* node, int64_t* source,
                                   hipStream_t st) {
-    hipLaunchKernelGGL(produce_write_kernel, grid_for(P.P), dim3(256), 0, st, (const STNodeDev*)nodes, P, path0,
-                       saved, seed, offsets, keys0, codes0, (ProducedRec*)recs, lost);
+    hipLaunchKernelGGL(produce_write_kernel, grid_for(P.P), dim3(256), 0, st, nodes, P, path0, saved, seed,
+                       offsets, keys0, codes0, (ProducedRec*)recs, lost);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || n_rec == 0) return e;
     // stable: a leaf's records stay in (path, push) order

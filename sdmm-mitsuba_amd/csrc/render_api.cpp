@@ -16,6 +16,8 @@
 
 #include "../../include/sdmm_gpu.h"
 #include "render_device.h"
+#include "render_launch.h"
+#include "host_xfer.h"
 #include "learned_bsdf.h"
 #include "bsdf_phong.h"
 #include "bsdf_roughdielectric.h"
@@ -23,38 +25,6 @@
 // the scene's derived quad data in plain IEEE float (no FMA contraction), as
 // the CPU restatement of Li forms it (oracle/sdmm_oracle_li.inc)
 #pragma clang fp contract(off)
-
-namespace sdmm {
-hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, int64_t path0, int spp, uint64_t seed,
-                            hipStream_t st);
-hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
-                           int max_depth, int guided, float h, uint64_t seed, hipStream_t st);
-hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
-                           int rr_depth, float h, uint64_t seed, int product, hipStream_t st);
-size_t li_select_temp_bytes(int64_t n);
-hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t n, int32_t* count_dev,
-                             void* temp, size_t temp_bytes, int product, hipStream_t st);
-hipError_t launch_li_film(const PathsDev& P, int64_t pix0, int64_t npix, int spp, int64_t plane, float* image,
-                          float* image_sqr, hipStream_t st);
-hipError_t launch_scene_intersect(const SceneDev& S, int64_t nq, const float* const o[3], const float* const d[3],
-                                  float mint, float maxt, int mode, int32_t* prim, float* t, hipStream_t st);
-hipError_t launch_env_eval(const SceneDev& S, int64_t nq, const float* const d[3], float* const rgb[3],
-                           hipStream_t st);
-hipError_t launch_roughdielectric(const float* bp, const float st[3], int64_t nq, const float* const wi[3],
-                                  const float* const* u, float* const wo[3], float* const value[3], float* pdf,
-                                  float* eta_out, hipStream_t st_);
-hipError_t launch_learned4(const float* rec, int M, float alpha, int64_t nq, const float* const wl[3], int keep,
-                           float* w, float* mean, float* cov, int32_t* n, hipStream_t st);
-hipError_t launch_learned_nd(int C, const float* rec, int M, const float* const* rest, const float* scal, int64_t nq,
-                             const float* const wl[3], int keep, int force, float* w, float* mean, float* cov,
-                             int32_t* n, hipStream_t st);
-}  // namespace sdmm
-
-namespace sdmm_detail {
-int set_error(int code, const char* msg);
-int tree_stream(sdmm_stree* t, hipStream_t* st);   // sdmm_api.cpp: device nodes uploaded, the tree's stream
-const int* tree_fallback_count(const sdmm_stree* t);   // sdmm_api.cpp
-}  // namespace sdmm_detail
 
 using namespace sdmm;
 

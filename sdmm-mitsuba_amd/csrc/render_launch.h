@@ -1,0 +1,45 @@
+// render_launch.h -- the host-callable functions render.hip defines for other
+// translation units, declared once (see launch.h).
+#pragma once
+
+#include "sdmm_device.h"
+#include "render_device.h"
+
+namespace sdmm {
+
+hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, int64_t path0, int spp, uint64_t seed,
+                            hipStream_t st);
+hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
+                           int max_depth, int guided, float h, uint64_t seed, hipStream_t st);
+hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
+                           int rr_depth, float h, uint64_t seed, int product, hipStream_t st);
+size_t li_select_temp_bytes(int64_t n);
+hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t n, int32_t* count_dev,
+                             void* temp, size_t temp_bytes, int product, hipStream_t st);
+hipError_t launch_li_film(const PathsDev& P, int64_t pix0, int64_t npix, int spp, int64_t plane, float* image,
+                          float* image_sqr, hipStream_t st);
+hipError_t launch_scene_intersect(const SceneDev& S, int64_t nq, const float* const o[3], const float* const d[3],
+                                  float mint, float maxt, int mode, int32_t* prim, float* t, hipStream_t st);
+hipError_t launch_env_eval(const SceneDev& S, int64_t nq, const float* const d[3], float* const rgb[3],
+                           hipStream_t st);
+hipError_t launch_roughdielectric(const float* bp, const float st[3], int64_t nq, const float* const wi[3],
+                                  const float* const* u, float* const wo[3], float* const value[3], float* pdf,
+                                  float* eta_out, hipStream_t st_);
+hipError_t launch_learned4(const float* rec, int M, float alpha, int64_t nq, const float* const wl[3], int keep,
+                           float* w, float* mean, float* cov, int32_t* n, hipStream_t st);
+hipError_t launch_learned_nd(int C, const float* rec, int M, const float* const* rest, const float* scal, int64_t nq,
+                             const float* const wl[3], int keep, int force, float* w, float* mean, float* cov,
+                             int32_t* n, hipStream_t st);
+
+// training records of a render's paths, routed to the spatial tree's leaves
+size_t produce_temp_bytes(int64_t n_paths, int64_t n_records, int key_bits);
+hipError_t launch_produce_count(const STNodeDev* nodes, const PathsDev& P, int64_t path0, int saved, uint64_t seed,
+                                int64_t* count, int64_t* offsets, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t launch_produce_records(const STNodeDev* nodes, int num_nodes, int key_bits, const PathsDev& P,
+                                  int64_t path0, int saved, uint64_t seed, const int64_t* offsets, int64_t n_rec,
+                                  uint32_t* keys0, uint32_t* keys1, int64_t* codes0, int64_t* codes1, void* recs,
+                                  void* temp, size_t temp_bytes, int64_t* seg_dev, int* lost, float* const x[6],
+                                  float* const nrm[3], float* w, uint8_t* stats, int32_t* node, int64_t* source,
+                                  hipStream_t st);
+
+}  // namespace sdmm

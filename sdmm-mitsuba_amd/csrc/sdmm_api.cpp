@@ -24,137 +24,10 @@
 #include "sdmm_device.h"
 #include "render_device.h"
 #include "host_xfer.h"
+#include "launch.h"
+#include "render_launch.h"
 
 #pragma clang fp contract(off)
-
-namespace sdmm {
-hipError_t launch_estep_resp(int cpl, int lps, const float* ep, int Kp, int K, const SamplesDev& s,
-                             int64_t n, int64_t chunk, float* resp, hipStream_t st);
-hipError_t launch_estep_stats(int cpl, int lps, const float* ep, int Kp, int K, const SamplesDev& s,
-                              int64_t n, int64_t chunk, int blocks, int wpb, float* partials,
-                              int pstride, hipStream_t st, const LeafDesc* leaves = nullptr,
-                              const int2* items = nullptr);
-hipError_t launch_reduce_finalize_batched(const float* partials, int pstride, int Kp, int K,
-                                          const LeafDesc* leaves, int n_leaves, hipStream_t st);
-hipError_t launch_mstep_batched(int K, int Kp, const MixDesc* mixes, int n_mix, float norm5, hipStream_t st);
-hipError_t launch_set_f64(double* p, double v, hipStream_t st);
-hipError_t estep_occupancy(int cpl, int lps, int Kp, int* resp_blocks, int* stats_blocks);
-hipError_t launch_estep_resp_tile(int variant, const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
-                                  int64_t chunk, float* resp, hipStream_t st);
-hipError_t estep_resp_tile_occupancy(int variant, int* blocks_per_cu);
-const char* estep_resp_tile_name(int variant);
-hipError_t launch_estep_resp_mfma(int variant, const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
-                                  int64_t chunk, float* resp, hipStream_t st);
-hipError_t estep_resp_mfma_occupancy(int variant, int Kp, int* blocks_per_cu);
-const char* estep_resp_mfma_name(int variant, int Kp);
-bool estep_resp_split_supported(int Kp);
-size_t estep_resp_image_bytes(int Kp);
-hipError_t launch_estep_resp_image(const float* ep, int Kp, void* img, hipStream_t st);
-hipError_t launch_estep_resp_split(int variant, const float* ep, const void* img, int Kp, int K, const SamplesDev& s,
-                                   int64_t n, int64_t resident_waves, float* resp, hipStream_t st);
-hipError_t estep_resp_split_occupancy(int variant, int Kp, bool inline_image, int* waves_per_cu);
-const char* estep_resp_split_name(int variant, int Kp, bool inline_image);
-hipError_t launch_estep_stats_tile(int variant, const float* ep, int Kp, int K, const SamplesDev& s, int64_t n,
-                                   int64_t chunk, int blocks, float* partials, int pstride, hipStream_t st,
-                                   const LeafDesc* leaves = nullptr, const int2* items = nullptr);
-hipError_t estep_stats_tile_occupancy(int variant, int Kp, int* blocks_per_cu);
-hipError_t launch_reduce_partials(const float* partials, int rows, int pstride, const float* ep_for_finalize,
-                                  int Kp, int K, double* stats, hipStream_t st);
-hipError_t launch_set_all(int K, int Kp, const double* mean, const double* cov, const CanonDev& C,
-                          float* ep, float* gp, float norm5, hipStream_t st);
-hipError_t launch_pack_all(int K, int Kp, const CanonDev& C, float* ep, float* gp, float norm5,
-                           hipStream_t st);
-hipError_t launch_init_state(int K, const double* scal, const float* bprior, float eps, double* sc, float* bp,
-                             float* bd, hipStream_t st);
-hipError_t launch_hemi_gen_batched(int n, int K, const float* pos, const float* nrm, const float* dist,
-                                   const uint64_t* seed, int skip, float depth_prior, void* staging, size_t per,
-                                   hipStream_t st);
-hipError_t launch_set_all_batched(int n, int K, int Kp, const void* tab, const void* staging, size_t per, float norm5,
-                                  hipStream_t st);
-hipError_t launch_copy_many(int n, const void* src_tab, const void* dst_tab, size_t bytes, hipStream_t st);
-hipError_t launch_gather_f64(const void* src_tab, int n, double* out, hipStream_t st);
-struct InitDescHost {
-    CanonDev C;
-    float *ep, *gp, *bp, *bd;
-    double *tmean, *tcov;
-};
-hipError_t launch_init_pack_many(int n, int K, int Kp, const double* scal, const float* bprior, float eps,
-                                 double* sc, float* bp, float* bd, const CanonDev& C, float* ep, float* gp,
-                                 float norm5, size_t stride, hipStream_t st);
-hipError_t launch_mstep(int K, int Kp, const double* stats, int64_t nSamples, const CanonDev& C,
-                        const EmStateDev& S, float* ep, float* gp, float norm5, double* newW, unsigned* count,
-                        hipStream_t st);
-size_t guide_sort_temp_bytes(int n);
-hipError_t launch_stree_find(const void* nodes, int64_t n, const float* p0, const float* p1, const float* p2,
-                             int32_t* out, hipStream_t st);
-size_t stree_route_temp_bytes(int n, int key_bits);
-hipError_t launch_stree_route(const void* nodes, int num_nodes, int key_bits, const SamplesDev& in, int n,
-                              uint32_t* keys0, uint32_t* keys1, int32_t* idx0, int32_t* idx1, void* temp,
-                              size_t temp_bytes, int64_t* seg_dev, float* const out_x[6], float* out_w,
-                              float* out_h, uint8_t* out_d, hipStream_t st);
-hipError_t launch_guide(const float* gp, int Kp, int K, int64_t nq, const float* const c[3],
-                        const float* const u[3], const float* const dgiven[3], float* const d[3], float* pdf,
-                        int32_t* comp, float norm2, float norm3, int cap, int* fb_count, int32_t* fb_list,
-                        int cus, hipStream_t st, const GuideSortScratch* sort, int* fb2 = nullptr);
-hipError_t launch_guide_tree(const void* nodes, const void* tab, int kmax, int64_t nq, const float* const c[3],
-                             const float* const u[3], const float* const dgiven[3], float* const d[3],
-                             float* pdf, int32_t* comp, int32_t* node_out, float norm2, float norm3, int cap,
-                             int* fb_count, int32_t* fb_list, int cus, hipStream_t st,
-                             const GuideSortScratch* sort, const uint8_t* pmode = nullptr, int* fb2 = nullptr,
-                             int nn = 0);
-hipError_t launch_guide_product(const float* gp, int Kp, int K, const float* condCov, int64_t nq,
-                                const float* const c[3], const float* const u[3], const float* const dgiven[3],
-                                float* const d[3], float* pdf, int32_t* comp, const int32_t* material,
-                                const float* const frame[9], float* h, const float* bw, const float* bmean,
-                                const float* bcov, const uint8_t* diffuse, int B, int M, float norm2, float norm3,
-                                int cap, int* fb_count, int32_t* fb_list, int cus, hipStream_t st,
-                                const GuideSortScratch* sort, ProductScratch* scratch);
-hipError_t launch_guide_product_tree(const void* nodes, const void* tab, const void* cctab, int kmax, int64_t nq,
-                                     const float* const c[3], const float* const u[3], const float* choice,
-                                     const float* const dgiven[3], float* const d[3], float* pdf, int32_t* comp,
-                                     int32_t* node_out, const int32_t* material, const float* const frame[9],
-                                     float* h, const float* bw, const float* bmean, const float* bcov,
-                                     const uint8_t* diffuse, int B, int M, float norm2, float norm3, int cap,
-                                     int* fb_count, int32_t* fb_list, int cus, hipStream_t st,
-                                     const GuideSortScratch* sort, ProductScratch* scratch, int nn = 0);
-#ifndef SDMM_GUIDE_CAP_MAX
-#define SDMM_GUIDE_CAP_MAX 64
-#endif
-constexpr int kGuideCapMax = SDMM_GUIDE_CAP_MAX;
-// default capacity: 40 (round 4 A/B, Cornell K=128 tree wavefront: 12.3 ms per
-// guided pass at 40 against 13.3 ms at 64 -- a third of the fallback queries
-// but 2 instead of 3 waves per SIMD; K=512 product 92.2 vs 91.4 ms; the single
-// K=128 mixture 613 vs 816 us)
-#ifndef SDMM_GUIDE_CAP_DEFAULT
-#define SDMM_GUIDE_CAP_DEFAULT 40
-#endif
-constexpr int kGuideCapDefault = SDMM_GUIDE_CAP_DEFAULT;
-hipError_t launch_split_load(const float* const p[3], const int64_t* src_start, const int64_t* dst_start, int n_items,
-                             int64_t total, float* ox, float* oy, float* oz, int32_t* oitem, hipStream_t st);
-hipError_t launch_split_sums(const float* x, const float* y, const float* z, const void* chunks, int n_chunks,
-                             double* partial, hipStream_t st);
-hipError_t launch_split_flags(const float* x, const float* y, const float* z, const int32_t* item, int64_t n,
-                              const void* cand, int n_items, int32_t* flags, int64_t* rank, void* temp,
-                              size_t temp_bytes, long long* counts, hipStream_t st);
-hipError_t launch_split_scatter(const float* x, const float* y, const float* z, const int32_t* item, int64_t n,
-                                const void* cand, const int32_t* flags, const int64_t* rank, float* ox, float* oy,
-                                float* oz, int32_t* oitem, hipStream_t st);
-hipError_t launch_split_decide(const void* items, int n_items, const double* partial, int threshold, void* cand,
-                               void* dec, hipStream_t st);
-size_t split_scan_temp_bytes(int64_t n);
-int split_chunk_samples();
-hipError_t launch_sample_cdf(const float* cdf, int n, const float* u, int64_t nq, int32_t* out,
-                             hipStream_t st);
-hipError_t launch_produce_count(const void* nodes, const PathsDev& P, int64_t path0, int saved, uint64_t seed,
-                                int64_t* count, int64_t* offsets, void* temp, size_t temp_bytes, hipStream_t st);
-hipError_t launch_produce_records(const void* nodes, int num_nodes, int key_bits, const PathsDev& P, int64_t path0,
-                                  int saved, uint64_t seed, const int64_t* offsets, int64_t n_rec, uint32_t* keys0,
-                                  uint32_t* keys1, int64_t* codes0, int64_t* codes1, void* recs, void* temp,
-                                  size_t temp_bytes, int64_t* seg_dev, int* lost, float* const x[6],
-                                  float* const nrm[3], float* w, uint8_t* stats, int32_t* node, int64_t* source,
-                                  hipStream_t st);
-size_t produce_temp_bytes(int64_t n_paths, int64_t n_records, int key_bits);
-}  // namespace sdmm
 
 using namespace sdmm;
 
@@ -172,8 +45,6 @@ int fail(int code, const std::string& msg) {
 // the error slot for the library's other host translation units (checkpoint.cpp)
 namespace sdmm_detail {
 int set_error(int code, const char* msg) { return fail(code, msg); }
-void destroy_impl(sdmm_mix* m, bool sync);
-void destroy_many(sdmm_mix* const* ms, int n);
 }  // namespace sdmm_detail
 
 namespace {
@@ -469,16 +340,33 @@ struct Slab {
     hipStream_t st = nullptr;
 };
 
+// The E-step kernels of a mixture, chosen once at creation (choose_resp, choose_stats)
+enum class RespKernel {
+    Legacy,   // estep_resp_kernel<cpl, lps> (every K)
+    Tile,     // estep_resp_tile_kernel (64 < K <= 128)
+    Mfma,     // estep_resp_mfma_kernel (f32 matrix cores, every K)
+    Split,    // estep_resp_split[_band]_kernel (bf16x3 MFMA forms, Kp <= 128)
+};
+enum class StatsKernel {
+    Legacy,   // estep_stats_kernel<cpl, lps> (K <= 64)
+    Tile,     // estep_stats_tile_kernel (64 < K <= 128)
+    Group,    // its GROUP form (128 < K <= 512: Kp / 128 waves per chunk)
+};
+struct RespChoice {
+    RespKernel kernel = RespKernel::Legacy;
+    int cpl = 2, lps = 64;       // the legacy kernel's layout (same Kp); what sdmm_layout reports
+    bool lds_image = false;      // Split: the coefficient image in LDS (SDMM_RESP_KERNEL=splitlds)
+    bool inline_image = false;   // SDMM_RESP_IMAGE=inline: every Split workgroup builds its own image
+    bool operator==(const RespChoice& o) const {
+        return kernel == o.kernel && cpl == o.cpl && lps == o.lps && lds_image == o.lds_image &&
+               inline_image == o.inline_image;
+    }
+};
+
 struct sdmm_mix {
     int K = 0, Kp = 0, cpl = 1, lps = 64;   // statistics E-step layout
-    int rcpl = 2, rlps = 64;                 // responsibility E-step layout (same Kp)
-    int rtile = 0;                           // 1: estep_resp_tile_kernel (64 < K <= 128)
-                                             // 2: estep_resp_mfma_kernel (every K)
-                                             // 3: estep_resp_split_kernel (bf16x3 MFMA forms, Kp <= 128)
-    int rvariant = 4;                        // tile / mfma kernel variant: KT=8, 3 waves/SIMD
-    int stile = 0;                           // 1: estep_stats_tile_kernel (64 < K <= 128)
-                                             // 2: its GROUP form (128 < K <= 512: Kp / 128 waves per chunk)
-    int svariant = 0;                        // its occupancy variant
+    RespChoice rk;                           // responsibility E-step kernel
+    StatsKernel sk = StatsKernel::Legacy;    // statistics E-step kernel
     int device = 0;
     int cus = 256;
     int resp_blocks = 2, stats_blocks = 2;   // resident 256-thread WGs per CU
@@ -505,7 +393,6 @@ struct sdmm_mix {
     // the split kernel's coefficient image of ep (estep_split.hip): allocated
     // and built by the first sdmm_responsibilities that needs it, rebuilt when
     // ep has been written since (ep_written), never copied to a clone
-    bool rimg_inline = false;    // SDMM_RESP_IMAGE=inline: every workgroup builds its own
     void* rimg = nullptr;
     uint64_t ep_epoch = 1;       // bumped wherever a writer of ep is enqueued
     uint64_t rimg_epoch = 0;     // the ep_epoch rimg was built at (0: never)
@@ -627,6 +514,42 @@ int choose_layout(int K, int& cpl, int& lps) {
     return 0;
 }
 
+// The responsibility kernel for K components (Kp padded) under the values of
+// SDMM_RESP_KERNEL and SDMM_RESP_IMAGE (null: unset).  64 < K <= 128
+// (Kp = 128): the bf16x3 split-MFMA kernel (estep_split.hip: the eight linear
+// forms on the matrix cores, the rest packed f32; 186 vs 204 us per 2^20
+// samples); other K: the legacy kernel.  SDMM_RESP_KERNEL
+// selects the others for A/B measurements: tile (the VALU form, Kp = 128
+// only), mfma (f32 matrix cores, every K), legacy; split also for other K with
+// Kp / 16 in {1, 2, 4}; splitlds the split kernel with the coefficient image
+// in LDS at Kp = 128 (the default there keeps it in registers).  A kernel that
+// does not support K falls through to the default.  The legacy layout for
+// 64 < K <= 128 is 4 components per lane, 2 samples per wave (half the
+// reduction overhead per pair, two independent packed chains per lane).
+RespChoice choose_resp(int K, int Kp, const char* kernel_env, const char* image_env) {
+    const auto is = [](const char* v, const char* name) { return v && std::strcmp(v, name) == 0; };
+    const bool k128 = K > 64 && K <= 128;
+    RespChoice c;
+    (void)choose_layout(K, c.cpl, c.lps);
+    if (k128) { c.cpl = 4; c.lps = 32; }
+    const bool splitlds = is(kernel_env, "splitlds");
+    const bool split_ok = estep_resp_split_supported(Kp);
+    if (is(kernel_env, "mfma")) c.kernel = RespKernel::Mfma;
+    else if ((splitlds || is(kernel_env, "split")) && split_ok) c.kernel = RespKernel::Split;
+    else if (k128 && !is(kernel_env, "legacy"))
+        c.kernel = (is(kernel_env, "tile") || !split_ok) ? RespKernel::Tile : RespKernel::Split;
+    if (k128 && (c.kernel == RespKernel::Tile || c.kernel == RespKernel::Split)) { c.cpl = 2; c.lps = 64; }
+    c.lds_image = splitlds && c.kernel == RespKernel::Split;
+    c.inline_image = is(image_env, "inline");
+    return c;
+}
+
+// statistics: the tile kernel for 64 < K <= 128, its GROUP form for
+// 128 < K <= 512 (estep.hip), estep_stats_kernel otherwise
+StatsKernel choose_stats(int K) {
+    return K > 128 ? StatsKernel::Group : (K > 64 ? StatsKernel::Tile : StatsKernel::Legacy);
+}
+
 // Work split of an E-step launch: contiguous chunk of samples per wave.
 struct Split {
     int64_t chunk;
@@ -722,7 +645,7 @@ struct StatsPlan {
     int blocks;
 };
 StatsPlan stats_plan(const sdmm_mix* m, int64_t n) {
-    if (m->stile == 2) {
+    if (m->sk == StatsKernel::Group) {
         // GROUP form: a workgroup (Kp / 128 waves) per chunk; one round of
         // resident workgroups, chunks of whole 64-sample blocks
         const int64_t resident = (int64_t)m->cus * (m->stats_blocks > 0 ? m->stats_blocks : 1);
@@ -732,7 +655,7 @@ StatsPlan stats_plan(const sdmm_mix* m, int64_t n) {
         const int64_t blocks = (n + chunk - 1) / chunk;
         return StatsPlan{chunk, (int)(blocks > 0 ? blocks : 1)};
     }
-    if (m->stile) {
+    if (m->sk == StatsKernel::Tile) {
         // one round of resident waves, each a whole number of 64-sample blocks
         const int64_t resident = (int64_t)m->cus * 4 * (m->stats_blocks > 0 ? m->stats_blocks : 1);
         int64_t chunk = (n + resident - 1) / resident;
@@ -747,11 +670,98 @@ StatsPlan stats_plan(const sdmm_mix* m, int64_t n) {
 
 hipError_t launch_stats_kernel(const sdmm_mix* m, const SamplesDev& d, int64_t n, const StatsPlan& p, int blocks,
                                float* partials, hipStream_t st, const LeafDesc* leaves, const int2* items) {
-    if (m->stile)
-        return launch_estep_stats_tile(m->svariant, m->ep, m->Kp, m->K, d, n, p.chunk, blocks, partials, m->pstride,
+    if (m->sk != StatsKernel::Legacy)
+        return launch_estep_stats_tile(m->ep, m->Kp, m->K, d, n, p.chunk, blocks, partials, m->pstride,
                                        st, leaves, items);
     return launch_estep_stats(m->cpl, m->lps, m->ep, m->Kp, m->K, d, n, p.chunk, blocks, 4, partials, m->pstride,
                               st, leaves, items);
+}
+
+// Resident workgroups per CU of m's statistics kernel.
+hipError_t stats_occupancy(const sdmm_mix* m, int* blocks) {
+    int unused = 0;
+    if (m->sk == StatsKernel::Legacy) return estep_occupancy(m->cpl, m->lps, m->Kp, &unused, blocks);
+    return estep_stats_tile_occupancy(m->Kp, blocks);
+}
+
+const char* stats_name(const sdmm_mix* m) {
+    static thread_local char buf[64];
+    if (m->sk == StatsKernel::Tile) return "estep_stats_tile_kernel<4,2>";
+    if (m->sk == StatsKernel::Group) std::snprintf(buf, sizeof buf, "estep_stats_tile_kernel<%d,2,true>", m->Kp / 128);
+    else std::snprintf(buf, sizeof buf, "estep_stats_kernel<%d,%d>", m->cpl, m->lps);
+    return buf;
+}
+
+// m->resp_blocks: resident 256-thread workgroups per CU (Split: resident waves per CU)
+hipError_t resp_occupancy(const sdmm_mix* m, int* blocks) {
+    const RespChoice& c = m->rk;
+    int unused = 0;
+    switch (c.kernel) {
+    case RespKernel::Legacy: return estep_occupancy(c.cpl, c.lps, m->Kp, blocks, &unused);
+    case RespKernel::Tile: return estep_resp_tile_occupancy(blocks);
+    case RespKernel::Mfma: return estep_resp_mfma_occupancy(m->Kp, blocks);
+    case RespKernel::Split: return estep_resp_split_occupancy(c.lds_image, m->Kp, c.inline_image, blocks);
+    }
+    return hipErrorInvalidValue;
+}
+
+const char* resp_name(const sdmm_mix* m) {
+    static thread_local char buf[64];
+    const RespChoice& c = m->rk;
+    switch (c.kernel) {
+    case RespKernel::Legacy: std::snprintf(buf, sizeof buf, "estep_resp_kernel<%d,%d>", c.cpl, c.lps); return buf;
+    case RespKernel::Tile: return estep_resp_tile_name();
+    case RespKernel::Mfma: return estep_resp_mfma_name(m->Kp);
+    case RespKernel::Split: return estep_resp_split_name(c.lds_image, m->Kp, c.inline_image);
+    }
+    return "";
+}
+
+// Enqueues m's responsibility kernel over the n samples of d.
+int launch_resp(sdmm_mix* m, const SamplesDev& d, int64_t n, float* resp) {
+    const RespChoice& c = m->rk;
+    const int rb = m->resp_blocks > 0 ? m->resp_blocks : 1;
+    switch (c.kernel) {
+    case RespKernel::Split: {
+        const int64_t resident = (int64_t)m->cus * rb;
+        if (!c.inline_image && m->rimg_epoch != m->ep_epoch) {
+            // the image of the current ep, behind ep's last writer on the stream
+            // and ahead of the kernel that reads it (where the in-kernel build reads ep)
+            if (!m->rimg) HIP_TRY(hipMalloc(&m->rimg, estep_resp_image_bytes(m->Kp)));
+            HIP_TRY(launch_estep_resp_image(m->ep, m->Kp, m->rimg, m->stream));
+            m->rimg_epoch = m->ep_epoch;
+            ++m->rimg_builds;
+        }
+        HIP_TRY(launch_estep_resp_split(c.lds_image, m->ep, c.inline_image ? nullptr : m->rimg, m->Kp, m->K, d, n,
+                                        resident, resp, m->stream));
+        break;
+    }
+    case RespKernel::Mfma: {
+        // chunks of whole 16-sample tiles, ~3 rounds of resident waves
+        const int64_t resident = (int64_t)m->cus * 4 * rb;
+        int64_t chunk = (n + 3 * resident - 1) / (3 * resident);
+        chunk = ((chunk + 15) / 16) * 16;
+        if (chunk < 64) chunk = 64;
+        HIP_TRY(launch_estep_resp_mfma(m->ep, m->Kp, m->K, d, n, chunk, resp, m->stream));
+        break;
+    }
+    case RespKernel::Tile: {
+        // chunks of whole 64-sample blocks; ~3 rounds of resident waves so the
+        // tail of the launch stays short
+        const int64_t resident = (int64_t)m->cus * 4 * rb;
+        int64_t chunk = (n + 3 * resident - 1) / (3 * resident);
+        chunk = ((chunk + 63) / 64) * 64;
+        if (chunk < 64) chunk = 64;   // one staged 64-sample block: small (per-rank) batches still fill the chip
+        HIP_TRY(launch_estep_resp_tile(m->ep, m->Kp, m->K, d, n, chunk, resp, m->stream));
+        break;
+    }
+    case RespKernel::Legacy: {
+        const Split sp = split_for(m, n, c.lps, m->resp_blocks);
+        HIP_TRY(launch_estep_resp(c.cpl, c.lps, m->ep, m->Kp, m->K, d, n, sp.chunk, resp, m->stream));
+        break;
+    }
+    }
+    return SDMM_OK;
 }
 
 int run_estep_stats(sdmm_mix* m, const sdmm_samples* s, double* stats_out) {
@@ -872,7 +882,8 @@ void constructor_scalars(const sdmm_mix* m, double* scal) {
 // E-step occupancy per K and kernel choice (the layout depends on K and the
 // process's environment only): queried once per combination
 struct OccCache {
-    int K = -1, kern = -1, resp = 0, stats = 0;
+    int K = -1, resp = 0, stats = 0;
+    RespChoice rk;
 };
 
 int create_impl(int K, const sdmm_em_params* params, int device, hipStream_t ordered, bool on_stream,
@@ -898,70 +909,18 @@ int create_impl(int K, const sdmm_em_params* params, int device, hipStream_t ord
     if (hipSetDevice(device) != hipSuccess) return cleanup(fail(SDMM_E_HIP, "hipSetDevice failed"));
     (void)hipDeviceGetAttribute(&m->cus, hipDeviceAttributeMultiprocessorCount, device);
     if (m->cus <= 0) m->cus = 256;
-    // responsibilities: for 64 < K <= 128, 4 components per lane and 2 samples
-    // per wave halve the per-sample reduction/normalisation overhead per pair
-    // and give each lane two independent packed chains (same Kp = 128)
-    m->rcpl = cpl;
-    m->rlps = lps;
-    if (K > 64 && K <= 128) { m->rcpl = 4; m->rlps = 32; }
-    // 64 < K <= 128 (Kp = 128): the bf16x3 split-MFMA kernel (estep_split.hip:
-    // the eight linear forms on the matrix cores, the rest packed f32; 186 vs
-    // 204 us per 2^20 samples).  SDMM_RESP_KERNEL selects
-    // the others for A/B measurements: tile (estep_resp_tile_kernel, the VALU
-    // form), mfma (f32 matrix cores, estep_mfma.hip), legacy
-    // (estep_resp_kernel<4,32>); split also for other K with Kp / 16 in {1, 2, 4};
-    // splitlds the split kernel with the coefficient image in LDS at Kp = 128
-    // (the default there keeps it in registers: estep_resp_split_band_kernel).
-    {
-        const char* ev = std::getenv("SDMM_RESP_KERNEL");
-        const bool legacy = ev && std::strcmp(ev, "legacy") == 0;
-        const bool mfma = ev && std::strcmp(ev, "mfma") == 0;
-        const bool tile = ev && std::strcmp(ev, "tile") == 0;
-        const bool splitlds = ev && std::strcmp(ev, "splitlds") == 0;
-        const bool split = splitlds || (ev && std::strcmp(ev, "split") == 0);
-        if (K > 64 && K <= 128 && !legacy && !mfma) {
-            m->rtile = 1;
-            m->rcpl = 2;
-            m->rlps = 64;
-            if (!tile && estep_resp_split_supported(m->Kp)) m->rtile = 3;
-        }
-        if (mfma) m->rtile = 2;
-        if (split && estep_resp_split_supported(m->Kp)) m->rtile = 3;
-        if (splitlds && m->rtile == 3) m->rvariant = 15;   // estep_split.hip kSplitLdsVariant
-        // SDMM_RESP_IMAGE=inline: the split kernel whose workgroups build the
-        // coefficient image themselves (A/B runs, the bitwise tests)
-        const char* iv = std::getenv("SDMM_RESP_IMAGE");
-        m->rimg_inline = iv && std::strcmp(iv, "inline") == 0;
-        // statistics: the tile kernel for 64 < K <= 128, its GROUP form for
-        // 128 < K <= 512 (estep.hip), estep_stats_kernel otherwise
-        if (K > 64 && K <= 128) m->stile = 1;
-        if (K > 128 && K <= 512) m->stile = 2;
-    }
+    m->rk = choose_resp(K, m->Kp, std::getenv("SDMM_RESP_KERNEL"), std::getenv("SDMM_RESP_IMAGE"));
+    m->sk = choose_stats(K);
     static thread_local OccCache occ[8];
     OccCache& oc = occ[(K * 7 + device) & 7];
-    const int kern = (((m->rtile * 16 + m->rvariant) * 16 + m->stile) * 16 + m->svariant) * 2 + (m->rimg_inline ? 1 : 0);
-    if (oc.K == K * 64 + device && oc.kern == kern) {
+    if (oc.K == K * 64 + device && oc.rk == m->rk) {
         m->resp_blocks = oc.resp;
         m->stats_blocks = oc.stats;
     } else {
-        int unused = 0;
-        if (estep_occupancy(m->rcpl, m->rlps, m->Kp, &m->resp_blocks, &unused) != hipSuccess ||
-            estep_occupancy(m->cpl, m->lps, m->Kp, &unused, &m->stats_blocks) != hipSuccess)
-            return cleanup(fail(SDMM_E_HIP, "E-step occupancy query failed"));
-        if (m->rtile == 2 && estep_resp_mfma_occupancy(m->rvariant, m->Kp, &m->resp_blocks) != hipSuccess)
-            return cleanup(fail(SDMM_E_HIP, "E-step occupancy query failed"));
-        if (m->rtile == 3) {
-            int wpc = 0;
-            if (estep_resp_split_occupancy(m->rvariant, m->Kp, m->rimg_inline, &wpc) != hipSuccess)
-                return cleanup(fail(SDMM_E_HIP, "E-step occupancy query failed"));
-            m->resp_blocks = wpc;   // resident waves per CU (split kernel)
-        }
-        if (m->rtile == 1 && estep_resp_tile_occupancy(m->rvariant, &m->resp_blocks) != hipSuccess)
-            return cleanup(fail(SDMM_E_HIP, "E-step occupancy query failed"));
-        if (m->stile && estep_stats_tile_occupancy(m->svariant, m->Kp, &m->stats_blocks) != hipSuccess)
+        if (resp_occupancy(m, &m->resp_blocks) != hipSuccess || stats_occupancy(m, &m->stats_blocks) != hipSuccess)
             return cleanup(fail(SDMM_E_HIP, "E-step occupancy query failed"));
         oc.K = K * 64 + device;
-        oc.kern = kern;
+        oc.rk = m->rk;
         oc.resp = m->resp_blocks;
         oc.stats = m->stats_blocks;
     }
@@ -1166,9 +1125,9 @@ int copy_prefix_many(const sdmm_mix* const* src, sdmm_mix* const* dst, int n, hi
     StreamScratch* ss = nullptr;
     std::unique_lock<std::mutex> hold = stream_scratch(src[0]->device, st, &ss);
     hipError_t e = scratch_reserve(*ss, tb);
-    void* dtab = ss->p;
+    uint4** dtab = (uint4**)ss->p;   // [n] sources, then [n] destinations
     if (e == hipSuccess) e = hipMemcpyAsync(dtab, ptrs, tb, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = launch_copy_many(n, dtab, (void**)dtab + n, bytes, st);
+    if (e == hipSuccess) e = launch_copy_many(n, dtab, dtab + n, bytes, st);
     {   // always: the bounce buffer and the table go to the next user
         const hipError_t es = hipStreamSynchronize(st);
         if (e == hipSuccess) e = es;
@@ -1254,8 +1213,8 @@ int sdmm_guide_fallback_count(const sdmm_mix* m, int* count) {
 
 int sdmm_layout(const sdmm_mix* m, int* resp_cpl, int* resp_lps, int* stats_cpl, int* stats_lps) {
     if (!m) return fail(SDMM_E_INVALID, "null handle");
-    if (resp_cpl) *resp_cpl = m->rcpl;
-    if (resp_lps) *resp_lps = m->rlps;
+    if (resp_cpl) *resp_cpl = m->rk.cpl;
+    if (resp_lps) *resp_lps = m->rk.lps;
     if (stats_cpl) *stats_cpl = m->cpl;
     if (stats_lps) *stats_lps = m->lps;
     return SDMM_OK;
@@ -1269,28 +1228,7 @@ int sdmm_resp_image_builds(const sdmm_mix* m, int64_t* count) {
 
 const char* sdmm_kernel_name(const sdmm_mix* m, int which) {
     if (!m) return "";
-    static thread_local char buf[64];
-    if (which == 0) {
-        if (m->rtile == 3) {
-            std::snprintf(buf, sizeof buf, "%s", estep_resp_split_name(m->rvariant, m->Kp, m->rimg_inline));
-            return buf;
-        } else if (m->rtile == 2) {
-            std::snprintf(buf, sizeof buf, "%s", estep_resp_mfma_name(m->rvariant, m->Kp));
-            return buf;
-        } else if (m->rtile) {
-            std::snprintf(buf, sizeof buf, "%s", estep_resp_tile_name(m->rvariant));
-            return buf;
-        }
-        std::snprintf(buf, sizeof buf, "estep_resp_kernel<%d,%d>", m->rcpl, m->rlps);
-        return buf;
-    }
-    if (m->stile == 2)
-        std::snprintf(buf, sizeof buf, "estep_stats_tile_kernel<%d,2,true>", m->Kp / 128);
-    else if (m->stile)
-        std::snprintf(buf, sizeof buf, "estep_stats_tile_kernel<4,%d>", m->svariant == 1 ? 3 : 2);
-    else
-        std::snprintf(buf, sizeof buf, "estep_stats_kernel<%d,%d>", m->cpl, m->lps);
-    return buf;
+    return which == 0 ? resp_name(m) : stats_name(m);
 }
 
 int sdmm_set_stream(sdmm_mix* m, void* hip_stream) {
@@ -1425,7 +1363,7 @@ static int init_hemisphere_batched_impl(sdmm_mix* const* mixes, int n, const flo
         return e && std::atoi(e) != 0;
     }();
     const size_t stage_bytes = (per * (size_t)n + 255) / 256 * 256;
-    const size_t tab_bytes = (sizeof(InitDescHost) * (size_t)n + 255) / 256 * 256;
+    const size_t tab_bytes = (sizeof(InitDesc) * (size_t)n + 255) / 256 * 256;
     const size_t pn_bytes = sizeof(float) * 3 * (size_t)npos * (size_t)n;   // positions, then normals
     const size_t in_bytes = host_gen ? 0 : 2 * pn_bytes + sizeof(float) * (size_t)n + sizeof(uint64_t) * (size_t)n + 16;
     const size_t up_off = host_gen ? 0 : stage_bytes;   // device offset of what is uploaded
@@ -1464,10 +1402,10 @@ static int init_hemisphere_batched_impl(sdmm_mix* const* mixes, int n, const flo
         init_range(0, (int)((int64_t)n / nt));
         for (auto& x : th) x.join();
     }
-    InitDescHost* tab = (InitDescHost*)(pin + stage_bytes - up_off);
+    InitDesc* tab = (InitDesc*)(pin + stage_bytes - up_off);
     for (int i = 0; i < n; ++i) {
         sdmm_mix* m = mixes[i];
-        tab[i] = InitDescHost{m->C, m->ep, m->gp, m->S.bPriors, m->S.bDepth, m->tmp_mean, m->tmp_cov};
+        tab[i] = InitDesc{m->C, m->ep, m->gp, m->S.bPriors, m->S.bDepth, m->tmp_mean, m->tmp_cov};
         ep_written(m);
     }
     const size_t in_off = stage_bytes + tab_bytes;   // device offsets of the inputs
@@ -1491,7 +1429,8 @@ static int init_hemisphere_batched_impl(sdmm_mix* const* mixes, int n, const flo
                                      (const float*)(d + dist_off), (const uint64_t*)(d + seed_off), skip, depth_prior,
                                      d, per, st);
     if (!r && e0 == hipSuccess)
-        e0 = launch_set_all_batched(n, K, mixes[0]->Kp, d + stage_bytes, d, per, mixes[0]->norm5, st);
+        e0 = launch_set_all_batched(n, K, mixes[0]->Kp, (const InitDesc*)(d + stage_bytes), d, per, mixes[0]->norm5,
+                                    st);
     if (!r && e0 != hipSuccess) r = fail(SDMM_E_HIP, std::string("init_hemisphere_batched: ") + hipGetErrorString(e0));
     const hipError_t e = hipStreamSynchronize(st);   // the pinned staging is reused by the next call
     if (r) return r;
@@ -1548,7 +1487,7 @@ int sdmm_iterations_run(const sdmm_mix* const* mixes, int n, int* out) {
     char* db = (char*)m0->it_dev;
     double* vals = (double*)((char*)m0->it_host + tab_bytes);
     HIP_TRY(hipMemcpyAsync(db, src, sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_gather_f64(db, n, (double*)(db + tab_bytes), st));
+    HIP_TRY(launch_gather_f64((const double* const*)db, n, (double*)(db + tab_bytes), st));
     HIP_TRY(hipMemcpyAsync(vals, db + tab_bytes, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int i = 0; i < n; ++i) out[i] = (int)vals[i];
@@ -2062,43 +2001,7 @@ int sdmm_responsibilities(sdmm_mix* m, const sdmm_samples* s, float* resp) {
     int r = check_samples(s);
     if (r) return r;
     if (s->n == 0) return SDMM_OK;
-    if (m->rtile == 3) {
-        const int64_t resident = (int64_t)m->cus * (m->resp_blocks > 0 ? m->resp_blocks : 1);
-        if (!m->rimg_inline && m->rimg_epoch != m->ep_epoch) {
-            // the image of the current ep, behind ep's last writer on the stream
-            // and ahead of the kernel that reads it (where the in-kernel build reads ep)
-            if (!m->rimg) HIP_TRY(hipMalloc(&m->rimg, estep_resp_image_bytes(m->Kp)));
-            HIP_TRY(launch_estep_resp_image(m->ep, m->Kp, m->rimg, m->stream));
-            m->rimg_epoch = m->ep_epoch;
-            ++m->rimg_builds;
-        }
-        HIP_TRY(launch_estep_resp_split(m->rvariant, m->ep, m->rimg_inline ? nullptr : m->rimg, m->Kp, m->K, to_dev(s),
-                                        s->n, resident, resp, m->stream));
-        return SDMM_OK;
-    }
-    if (m->rtile == 2) {
-        // chunks of whole 16-sample tiles, ~3 rounds of resident waves
-        const int64_t resident = (int64_t)m->cus * 4 * (m->resp_blocks > 0 ? m->resp_blocks : 1);
-        int64_t chunk = (s->n + 3 * resident - 1) / (3 * resident);
-        chunk = ((chunk + 15) / 16) * 16;
-        if (chunk < 64) chunk = 64;
-        HIP_TRY(launch_estep_resp_mfma(m->rvariant, m->ep, m->Kp, m->K, to_dev(s), s->n, chunk, resp, m->stream));
-        return SDMM_OK;
-    }
-    if (m->rtile) {
-        // chunks of whole 64-sample blocks; ~3 rounds of resident waves so the
-        // tail of the launch stays short
-        const int64_t resident = (int64_t)m->cus * 4 * (m->resp_blocks > 0 ? m->resp_blocks : 1);
-        int64_t chunk = (s->n + 3 * resident - 1) / (3 * resident);
-        chunk = ((chunk + 63) / 64) * 64;
-        if (chunk < 64) chunk = 64;   // one staged 64-sample block: small (per-rank) batches still fill the chip
-        HIP_TRY(launch_estep_resp_tile(m->rvariant, m->ep, m->Kp, m->K, to_dev(s), s->n, chunk, resp, m->stream));
-        return SDMM_OK;
-    }
-    const Split sp = split_for(m, s->n, m->rlps, m->resp_blocks);
-    HIP_TRY(launch_estep_resp(m->rcpl, m->rlps, m->ep, m->Kp, m->K, to_dev(s), s->n, sp.chunk, resp,
-                              m->stream));
-    return SDMM_OK;
+    return launch_resp(m, to_dev(s), s->n, resp);
 }
 
 int sdmm_guide_batch(const sdmm_mix* m, int64_t nq, const float* const c[3], const float* const u[3],
@@ -2302,19 +2205,11 @@ struct STNodeHost {
     int child[2] = {-1, -1};
 };
 
-// host image of guide.hip's GuideMix (one per tree node)
-struct GuideMixHost {
-    const float* gp;
-    int Kp, K;
-    bool operator!=(const GuideMixHost& o) const { return gp != o.gp || Kp != o.Kp || K != o.K; }
-};
-static_assert(sizeof(GuideMixHost) == 16, "GuideMix");
-
 struct sdmm_stree {
     int device = 0;
     hipStream_t stream = nullptr;
     std::vector<STNodeHost> nodes;
-    void* dnodes = nullptr;
+    STNodeDev* dnodes = nullptr;
     size_t dnodes_cap = 0;
     bool dirty = true;
     void* scratch = nullptr;
@@ -2322,10 +2217,10 @@ struct sdmm_stree {
     bool own_stream = true;
     // guided wavefront: per-node mixture table (device + the host copy it
     // was uploaded from) and the guided-batch scratch
-    std::vector<GuideMixHost> tab_host;
+    std::vector<GuideMix> tab_host;
     std::vector<const float*> cc_host;   // per node: the mixture's condCov (product wavefront)
-    void* dtab = nullptr;                // [nn] GuideMix, then [nn] condCov pointers (dcctab)
-    void* dcctab = nullptr;
+    GuideMix* dtab = nullptr;            // [nn] GuideMix, then [nn] condCov pointers (dcctab)
+    const float** dcctab = nullptr;
     size_t dtab_cap = 0;
     int tab_kmax = 0;
     int tab_cap = kGuideCapDefault; // candidate capacity: the smallest of the bound mixtures' (sdmm_set_guide_capacity)
@@ -2572,22 +2467,21 @@ int st_upload(sdmm_stree* t) {
     if (!t->stream && !t->stream_set) HIP_TRY(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
     if (!t->dirty) return SDMM_OK;
     t->published = false;
-    const size_t bytes = 32 * t->nodes.size();
+    const size_t bytes = sizeof(STNodeDev) * t->nodes.size();
     if (bytes > t->dnodes_cap) {
         HIP_TRY(hipStreamSynchronize(t->stream));
         release_dev(t->dnodes);
         t->dnodes = nullptr;
         const size_t cap = bytes * 2 > 4096 ? bytes * 2 : 4096;
-        HIP_TRY(hipMalloc(&t->dnodes, cap));
+        HIP_TRY(hipMalloc((void**)&t->dnodes, cap));
         t->dnodes_cap = cap;
     }
-    std::vector<float> rec(8 * t->nodes.size());
+    std::vector<STNodeDev> rec(t->nodes.size());
     for (size_t i = 0; i < t->nodes.size(); ++i) {
         const STNodeHost& n = t->nodes[i];
-        for (int a = 0; a < 3; ++a) { rec[8 * i + a] = n.mn[a]; rec[8 * i + 3 + a] = n.mx[a]; }
-        int c0 = n.child[0], c1 = n.child[1];
-        std::memcpy(&rec[8 * i + 6], &c0, 4);
-        std::memcpy(&rec[8 * i + 7], &c1, 4);
+        for (int a = 0; a < 3; ++a) { rec[i].mn[a] = n.mn[a]; rec[i].mx[a] = n.mx[a]; }
+        rec[i].c0 = n.child[0];
+        rec[i].c1 = n.child[1];
     }
     HIP_TRY(hipMemcpyAsync(t->dnodes, rec.data(), bytes, hipMemcpyHostToDevice, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));   // rec is a host temporary
@@ -3145,16 +3039,16 @@ namespace {
 // (the host copy stays alive as the source of the async copy until then).
 int st_upload_table(sdmm_stree* t, const sdmm_mix* const* node_mix) {
     const size_t nn = t->nodes.size();
-    std::vector<GuideMixHost> tab(nn);
+    std::vector<GuideMix> tab(nn);
     std::vector<const float*> cc(nn, nullptr);
     int kmax = 0, cap = kGuideCapMax;   // (lowered to the bound mixtures' capacities)
     t->mix_streams.clear();
     for (size_t i = 0; i < nn; ++i) {
         const sdmm_mix* m = node_mix[i];
-        tab[i] = GuideMixHost{nullptr, 0, 0};
+        tab[i] = GuideMix{nullptr, 0, 0};
         if (!m || !m->initialised) continue;
         if (m->device != t->device) return fail(SDMM_E_INVALID, "wavefront: mixture on another device");
-        tab[i] = GuideMixHost{m->gp, m->Kp, m->K};
+        tab[i] = GuideMix{m->gp, m->Kp, m->K};
         cc[i] = m->C.condCov;
         kmax = std::max(kmax, m->K);
         cap = std::min(cap, m->guide_cap);
@@ -3168,7 +3062,10 @@ int st_upload_table(sdmm_stree* t, const sdmm_mix* const* node_mix) {
         t->mix_events.push_back(e);
     }
     bool same = tab.size() == t->tab_host.size() && cc == t->cc_host;
-    for (size_t i = 0; same && i < nn; ++i) same = !(tab[i] != t->tab_host[i]);
+    for (size_t i = 0; same && i < nn; ++i) {
+        const GuideMix &a = tab[i], &b = t->tab_host[i];
+        same = a.gp == b.gp && a.Kp == b.Kp && a.K == b.K;
+    }
     t->tab_kmax = kmax;
     t->tab_cap = cap;
     t->tab_valid = true;
@@ -3176,17 +3073,17 @@ int st_upload_table(sdmm_stree* t, const sdmm_mix* const* node_mix) {
     t->published = false;
     HIP_TRY(hipStreamSynchronize(t->stream));   // the previous copy may still read tab_host
     const size_t nb = nn ? nn : 1;
-    const size_t bytes = (sizeof(GuideMixHost) + sizeof(const float*)) * nb;
+    const size_t bytes = (sizeof(GuideMix) + sizeof(const float*)) * nb;
     if (bytes > t->dtab_cap) {
         release_dev(t->dtab);
         t->dtab = nullptr;
-        HIP_TRY(hipMalloc(&t->dtab, bytes));
+        HIP_TRY(hipMalloc((void**)&t->dtab, bytes));
         t->dtab_cap = bytes;
     }
-    t->dcctab = (char*)t->dtab + sizeof(GuideMixHost) * nb;
+    t->dcctab = (const float**)((char*)t->dtab + sizeof(GuideMix) * nb);
     t->tab_host.swap(tab);
     t->cc_host.swap(cc);
-    HIP_TRY(hipMemcpyAsync(t->dtab, t->tab_host.data(), sizeof(GuideMixHost) * nn, hipMemcpyHostToDevice,
+    HIP_TRY(hipMemcpyAsync(t->dtab, t->tab_host.data(), sizeof(GuideMix) * nn, hipMemcpyHostToDevice,
                            t->stream));
     HIP_TRY(hipMemcpyAsync(t->dcctab, t->cc_host.data(), sizeof(const float*) * nn, hipMemcpyHostToDevice,
                            t->stream));
@@ -3544,23 +3441,7 @@ int tree_stream(sdmm_stree* t, hipStream_t* st) {
     *st = t->stream;
     return SDMM_OK;
 }
-// the device count of full-K (fallback) queries of the tree's last guided call
 const int* tree_fallback_count(const sdmm_stree* t) { return t->guide_fb; }
-}  // namespace sdmm_detail
-
-extern "C" {
-
-}  // extern "C"
-
-namespace sdmm_detail {
-// sdmm_push_training with reuse_counts: the call directly follows a count-only
-// call with the same tree, paths, saved_per_path and seed, so the per-path
-// record offsets still in the tree's scratch are reused (no second producer
-// count pass, no second synchronisation).  Without seg and lost nothing is read
-// back: the call returns with the writes in flight on the tree's stream.
-int push_training_ex(sdmm_stree* t, const sdmm_path_vertices* v, int saved_per_path, uint64_t seed,
-                     const sdmm_training_out* out, int64_t* n_out, int64_t* seg, int64_t* lost, bool reuse_counts,
-                     int64_t known_count);
 }  // namespace sdmm_detail
 
 extern "C" {

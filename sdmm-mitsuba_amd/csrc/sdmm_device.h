@@ -160,6 +160,21 @@ struct MixDesc {
     int64_t n;
     const double* ncount;   // non-null: the sample count is *ncount (all-reduced over ranks)
 };
+// Batched initialisation operands of one mixture (set_all_batched_kernel: one
+// workgroup each; the table the host uploads)
+struct InitDesc {
+    CanonDev C;
+    float *ep, *gp, *bp, *bd;
+    double *tmean, *tcov;
+};
+
+// One mixture's guide record as the wavefront kernels see it (per tree node;
+// K = 0: the node has no trained mixture -> BSDF only, sdmm_proc.cpp:316-323).
+struct GuideMix {
+    const float* gp;
+    int Kp, K;
+};
+static_assert(sizeof(GuideMix) == 16, "GuideMix");
 
 // scratch of the coherent (Morton) ordering of a guided batch
 struct GuideSortScratch {

@@ -10,6 +10,7 @@
 // split the parent's box, so the recursion is a single descent here: the
 // first child whose box contains the point.
 #include "sdmm_device.h"
+#include "launch.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -65,11 +66,11 @@ __global__ void stree_gather_kernel(SamplesDev in, int n, const int32_t* __restr
     if (od) od[j] = in.isDiffuse[i];
 }
 
-hipError_t launch_stree_find(const void* nodes, int64_t n, const float* p0, const float* p1, const float* p2,
+hipError_t launch_stree_find(const STNodeDev* nodes, int64_t n, const float* p0, const float* p1, const float* p2,
                              int32_t* out, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(stree_find_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                       (const STNodeDev*)nodes, n, p0, p1, p2, out);
+                       nodes, n, p0, p1, p2, out);
     return hipGetLastError();
 }
 
@@ -81,12 +82,11 @@ size_t stree_route_temp_bytes(int n, int key_bits) {
 }
 
 // keys/idx: 2 x n each; seg_dev: num_nodes + 2 int64; out planes: n each
-hipError_t launch_stree_route(const void* nodes, int num_nodes, int key_bits, const SamplesDev& in, int n,
+hipError_t launch_stree_route(const STNodeDev* nodes, int num_nodes, int key_bits, const SamplesDev& in, int n,
                               uint32_t* keys0, uint32_t* keys1, int32_t* idx0, int32_t* idx1, void* temp,
                               size_t temp_bytes, int64_t* seg_dev, float* const out_x[6], float* out_w,
                               float* out_h, uint8_t* out_d, hipStream_t st) {
-    const STNodeDev* nd = (const STNodeDev*)nodes;
-    hipLaunchKernelGGL(stree_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, nd, num_nodes, n,
+    hipLaunchKernelGGL(stree_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, nodes, num_nodes, n,
                        in.x[0], in.x[1], in.x[2], keys0, idx0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -115,8 +115,6 @@ hipError_t launch_stree_route(const void* nodes, int num_nodes, int key_bits, co
 namespace sdmm {
 
 constexpr int kSplitChunk = 4096;   // samples per reduction chunk (= the host's split_sums)
-
-
 
 // per chunk: the fp64 sums (p0, p1, p2, p0^2, p1^2, p2^2) in the canonical
 // order: lane t sums samples t, t + 256, ... ; the 256 lane sums fold by a
@@ -301,50 +299,46 @@ hipError_t launch_split_load(const float* const p[3], const int64_t* src_start, 
     return hipGetLastError();
 }
 
-hipError_t launch_split_sums(const float* x, const float* y, const float* z, const void* chunks, int n_chunks,
+hipError_t launch_split_sums(const float* x, const float* y, const float* z, const SplitChunkDev* chunks,
+                             int n_chunks,
                              double* partial, hipStream_t st) {
     if (n_chunks <= 0) return hipSuccess;
-    hipLaunchKernelGGL(split_sums_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, x, y, z,
-                       (const SplitChunkDev*)chunks, partial);
+    hipLaunchKernelGGL(split_sums_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, x, y, z, chunks, partial);
     return hipGetLastError();
 }
 
 // flags + exclusive scan (2 n + 1 entries) + the children's counts per item
 hipError_t launch_split_flags(const float* x, const float* y, const float* z, const int32_t* item, int64_t n,
-                              const void* cand, int n_items, int32_t* flags, int64_t* rank, void* temp,
+                              const SplitCandDev* cand, int n_items, int32_t* flags, int64_t* rank, void* temp,
                               size_t temp_bytes, long long* counts, hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(split_flags_kernel, split_grid(n), dim3(256), 0, st, x, y, z, item, n,
-                       (const SplitCandDev*)cand, flags);
+    hipLaunchKernelGGL(split_flags_kernel, split_grid(n), dim3(256), 0, st, x, y, z, item, n, cand, flags);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     e = hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, flags, rank, (int)(2 * n + 1), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(split_counts_kernel, split_grid(n_items), dim3(256), 0, st, (const SplitCandDev*)cand,
-                       n_items, rank, counts);
+    hipLaunchKernelGGL(split_counts_kernel, split_grid(n_items), dim3(256), 0, st, cand, n_items, rank, counts);
     return hipGetLastError();
 }
 
-hipError_t launch_split_decide(const void* items, int n_items, const double* partial, int threshold, void* cand,
-                               void* dec, hipStream_t st) {
+hipError_t launch_split_decide(const SplitItemDev* items, int n_items, const double* partial, int threshold,
+                               SplitCandDev* cand, SplitDecisionDev* dec, hipStream_t st) {
     if (n_items <= 0) return hipSuccess;
-    hipLaunchKernelGGL(split_decide_kernel, split_grid(n_items), dim3(256), 0, st, (const SplitItemDev*)items,
-                       n_items, partial, threshold, (SplitCandDev*)cand, (SplitDecisionDev*)dec);
+    hipLaunchKernelGGL(split_decide_kernel, split_grid(n_items), dim3(256), 0, st, items, n_items, partial,
+                       threshold, cand, dec);
     return hipGetLastError();
 }
 
 // the stable partition of the accepted splits into the next level
 hipError_t launch_split_scatter(const float* x, const float* y, const float* z, const int32_t* item, int64_t n,
-                                const void* cand, const int32_t* flags, const int64_t* rank, float* ox, float* oy,
-                                float* oz, int32_t* oitem, hipStream_t st) {
+                                const SplitCandDev* cand, const int32_t* flags, const int64_t* rank, float* ox,
+                                float* oy, float* oz, int32_t* oitem, hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(split_scatter_kernel, split_grid(n), dim3(256), 0, st, x, y, z, item, n,
-                       (const SplitCandDev*)cand, flags, rank, ox, oy, oz, oitem);
+    hipLaunchKernelGGL(split_scatter_kernel, split_grid(n), dim3(256), 0, st, x, y, z, item, n, cand, flags,
+                       rank, ox, oy, oz, oitem);
     return hipGetLastError();
 }
 
-size_t split_cand_bytes() { return sizeof(SplitCandDev); }
-size_t split_chunk_bytes() { return sizeof(SplitChunkDev); }
 int split_chunk_samples() { return kSplitChunk; }
 
 }  // namespace sdmm

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Per-launch times of the responsibility E-step on the bench workload
 (K = 128, N = 2^20, 5 warm EM steps): one event pair per launch, so a
-bimodal / drifting kernel shows up (SDMM_RESP_KERNEL / SDMM_RESP_VARIANT /
-SDMM_LIB_PATH select the build and configuration)."""
+bimodal / drifting kernel shows up (SDMM_RESP_KERNEL / SDMM_LIB_PATH
+select the build and configuration)."""
 import importlib
 import json
 import sys

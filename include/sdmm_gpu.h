@@ -995,7 +995,14 @@ int sdmm_mesh_bvh_dump(const sdmm_scene_desc* desc, int max_levels, int* n_nodes
  * *n_out = number of records (also when it exceeds capacity: then nothing is
  * written and SDMM_E_INVALID is returned; out NULL: count only); seg (host, nullable,
  * num_nodes + 1): leaf v's records are [seg[v], seg[v+1]).  lost (nullable):
- * vertices outside the tree (the reference throws).  Synchronous. */
+ * visited vertices outside the tree or at a NaN position (the reference
+ * throws), whatever their weight.  seg and lost are reported by a WRITING call
+ * only: a count-only call (out NULL) leaves seg untouched and sets *lost to 0
+ * although vertices may have been lost, and so does a call that returns
+ * SDMM_E_INVALID for its capacity.  n_paths = 0: *n_out = 0, seg all zero,
+ * *lost = 0.  The planes normal, stats, node and source of `out` are
+ * nullable; x and w are required once there is a record to write.
+ * Synchronous. */
 typedef struct {
     float* x[6];
     float* normal[3];        /* nullable (all three) */

@@ -415,11 +415,11 @@ def stree_find(aabb, child, pts):
     mn = np.ascontiguousarray(aabb[:, :3].reshape(-1), np.float32)
     mx = np.ascontiguousarray(aabb[:, 3:].reshape(-1), np.float32)
     ch = np.ascontiguousarray(child.reshape(-1), np.int32)
-    f = lib().or_stree_find
-    f.restype = C.c_int
-    out = np.empty(len(pts), np.int32)
-    for i, q in enumerate(np.ascontiguousarray(pts, np.float32)):
-        out[i] = f(_fp(mn), _fp(mx), ch.ctypes.data_as(C.c_void_p), _fp(q))
+    q = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+    out = np.empty(q.shape[0], np.int32)
+    f = lib().or_stree_find_many
+    f.restype = None
+    f(_fp(mn), _fp(mx), ch.ctypes.data_as(C.c_void_p), _fp(q), C.c_int64(q.shape[0]), out.ctypes.data_as(C.c_void_p))
     return out
 
 

@@ -102,6 +102,12 @@ int or_stree_find(const float* mn, const float* mx, const int* child, const floa
     return st_find_rec(&t, 0, p);
 }
 
+/* find for n points (pts[3 * i + a]) in one call */
+void or_stree_find_many(const float* mn, const float* mx, const int* child, const float* pts, int64_t n, int* out) {
+    st_tree t = {(float*)mn, (float*)mx, NULL, (int*)child, 0, 0};
+    for (int64_t i = 0; i < n; ++i) out[i] = st_find_rec(&t, 0, pts + 3 * i);
+}
+
 /* The split's fp64 sums over a node's samples in the library's one fixed
  * order (sdmm_api.cpp split_sums_host, stree.hip split_sums_kernel): chunks
  * of 4096 consecutive samples; in a chunk lane t of 256 sums samples t,

@@ -14,10 +14,14 @@ sdmm_guide_pdf_wavefront).
     estimators are unbiased) and whose variance is lower.
 The image itself is not compared with Mitsuba (none here; scenes.py).
 """
+import functools
 import importlib
 
 import numpy as np
 import pytest
+
+from guiding_host_loop import HostLoop, assert_same_mixtures as _assert_same_mixtures, from_device
+from producer_check import check_records
 
 pytestmark = pytest.mark.gpu
 
@@ -55,24 +59,7 @@ def _check_producer(pkg, oracle, tree, verts, saved, seed, plog, tag):
     V = verts.s.max_vertices
     aabb, child, _ = tree.nodes()
     ref = oracle.push_training(aabb, child, rec, nv, V, verts.s.path0, saved, seed)
-    order = np.argsort(ref["node"], kind="stable")        # the device's leaf order
-    for k in ("node", "source", "stats", "w"):
-        got = out[k].cpu().numpy()
-        want = ref[k][order]
-        assert got.shape == want.shape, (tag, k, got.shape, want.shape)
-        mism = int(np.sum(got.view(np.uint8) != want.view(np.uint8))) if k == "w" else int(np.sum(got != want))
-        plog(f"producer_{tag}_{k}_mismatches", mism, 0, records=int(got.size))
-        assert mism == 0, (tag, k)
-    src = out["source"].cpu().numpy()
-    P = nv.shape[0]
-    r = rec.reshape(16, V, P)
-    p, d = src // V, src % V
-    for i in range(6):
-        np.testing.assert_array_equal(out["x"][i].cpu().numpy(), r[7 + i][d, p])
-    for i in range(3):
-        np.testing.assert_array_equal(out["normal"][i].cpu().numpy(), r[13 + i][d, p])
-    counts = np.bincount(ref["node"], minlength=tree.num_nodes)
-    np.testing.assert_array_equal(out["seg"], np.concatenate([[0], np.cumsum(counts)]))
+    check_records(out, ref, rec, nv, V, tree.num_nodes, tag, plog)     # the comparisons shared with the constructed cases
     assert out["lost"] == 0 and ref["lost"] == 0
     n_jit = int(np.sum(out["stats"].cpu().numpy() == 0))
     assert n_jit > 0                                     # jittered copies went to neighbour leaves
@@ -93,134 +80,40 @@ def test_producer_matches_host_reference(pkg, oracle, scenes, gpu, plog):
     _check_producer(pkg, oracle, tree, verts, 3, 0x5EED + 1, plog, "saved3")
 
 
-def _subtree(child, v):
-    out, stack = [], [v]
-    while stack:
-        i = stack.pop()
-        out.append(i)
-        if child[i, 0] >= 0:
-            stack += [int(child[i, 0]), int(child[i, 1])]
-    return np.asarray(out)
+@functools.lru_cache(None)
+def _oracle():
+    """The oracle module the session fixture hands out, for _train's callers in
+    the other test files (they pass no oracle)."""
+    from oracle import oracle as o
+    o.build()
+    return o
 
 
 def _train(pkg, sc, tree, iterations, spp, K=16, seed=1, async_=False, state=None):
-    """The plugin's optimize() loop (volpath_sdmm.cpp:244-312, :411-507) on
-    the host side of the C-ABI: per leaf data + stats, split, canBeOptimized,
-    hemisphere init with 3 hmax(diag) / (K/8), 2 EM iterations while
-    iterations_run < 4, bind.  async_: optimize_async_run /
-    optimize_async_wait_and_update (:180-242) -- renders use the conditioners
-    (cond), refreshed after each pass from the leaves the previous EM stepped;
-    one EM step per leaf, init with 3 (0.1 hmax(diag)) / (K/8)."""
-    import torch
-    nn = lambda: tree.num_nodes
-    data = {}      # leaf -> list of record dicts (device)
-    stats = {}     # leaf -> list of positions (host)
-    mix = {}
-    cond = {}      # async: leaf -> conditioner
-    pending = []   # async: the leaves the running EM steps
-    total_spp = 0
-
-    def update():
-        for v in pending:
-            cond[v] = mix[v].clone()
-        pending.clear()
-
+    """The plugin's optimize() loop on the host side of the C-ABI
+    (guiding_host_loop.HostLoop: per leaf data + stats, split, canBeOptimized,
+    hemisphere init, 2 EM iterations while iterations_run < 4, bind; async_:
+    the renders use the conditioners, refreshed after each pass), fed with the
+    producer's records of a render per pass.  Rendered positions never lie on
+    a split plane, so the per-leaf split must build the tree the whole-tree
+    split_leaves builds: asserted at every split (whole_tree_check)."""
+    loop = HostLoop(pkg, _oracle(), tree, K=K, async_=async_, whole_tree_check=True)
     for it in range(iterations):
-        table = cond if async_ else mix
-        node_mix = [table.get(i) for i in range(nn())]
+        node_mix = loop.table()
         guided = any(m is not None for m in node_mix)
         _, verts, _ = sc.render(tree, node_mix if guided else None, spp=spp, guided=guided, seed=seed + it)
         out = tree.push_training(verts, 8, seed + 1000 + it)
-        update()
-        seg = out["seg"]
-        for v in range(nn()):
-            a, b = int(seg[v]), int(seg[v + 1])
-            if b > a:
-                data.setdefault(v, []).append({k: (out[k][a:b] if k in ("w",) else
-                                                   [t[a:b] for t in out[k]]) for k in ("x", "normal", "w")})
-                st = out["stats"][a:b].bool()
-                pos = torch.stack([t[a:b][st] for t in out["x"][:3]]).cpu().numpy()
-                stats.setdefault(v, []).append(pos)
-        # split by the leaves' stats positions (jmm createChildNode: a child keeps what its box holds)
-        old_n = nn()
-        allpos = np.concatenate([np.concatenate(stats[v], 1) for v in sorted(stats)], 1)
-        tree.split_leaves(allpos, threshold=4000, max_leaf_nodes=2048)
-        if nn() != old_n:
-            aabb, child, _ = tree.nodes()
-            for v in sorted(set(data) | set(stats) | set(mix)):
-                if child[v, 0] < 0:
-                    continue
-                # split: records, stats and mixture move to the children
-                sub = _subtree(child, v)
-                leaves = [int(i) for i in sub if child[i, 0] < 0]
-                for tab in (mix, cond):
-                    parent = tab.pop(v, None)
-                    if parent is not None:
-                        for c in leaves:
-                            tab[c] = parent.clone()
-                recs = data.pop(v, [])
-                if recs:
-                    x = [torch.cat([r["x"][i] for r in recs]) for i in range(6)]
-                    nr = [torch.cat([r["normal"][i] for r in recs]) for i in range(3)]
-                    w = torch.cat([r["w"] for r in recs])
-                    node = tree.find(x[:3]).cpu().numpy()
-                    node[~np.isin(node, sub)] = -1     # outside both children: dropped (jmm)
-                    for c in np.unique(node[node >= 0]):
-                        sel = torch.from_numpy(node == c).cuda()
-                        data.setdefault(int(c), []).append({"x": [t[sel] for t in x], "normal": [t[sel] for t in nr],
-                                                            "w": w[sel]})
-                pos = stats.pop(v, [])
-                if pos:
-                    ps = np.concatenate(pos, 1)
-                    pnode = tree.find([torch.from_numpy(ps[i].copy()).cuda() for i in range(3)]).cpu().numpy()
-                    pnode[~np.isin(pnode, sub)] = -1
-                    for c in np.unique(pnode[pnode >= 0]):
-                        stats.setdefault(int(c), []).append(ps[:, pnode == c])
-        aabb, child, _ = tree.nodes()
-        ready = []
-        for v, recs in data.items():
-            n_data = sum(int(r["w"].numel()) for r in recs)
-            n_stats = sum(p.shape[1] for p in stats.get(v, []))
-            if (total_spp > 12 or n_data > 1000) and child[v, 0] < 0 and n_stats >= 64 and n_data >= 8:
-                ready.append(v)
-        total_spp_now = total_spp
-        total_spp += spp                  # m_totalSpp grows after optimize() (volpath_sdmm.cpp:495-506)
-        if not ready:
-            continue
-        segs, xs, ws, its = [0], [[] for _ in range(6)], [], []
-        mixes = []
-        for v in ready:
-            recs = data.pop(v)
-            x = [torch.cat([r["x"][i] for r in recs]) for i in range(6)]
-            nr = [torch.cat([r["normal"][i] for r in recs]) for i in range(3)]
-            w = torch.cat([r["w"] for r in recs])
-            if v not in mix:
-                m = pkg.SDMM(K)
-                diag = np.max(aabb[v, 3:] - aabb[v, :3]).astype(np.float32)
-                if async_:
-                    diag = np.float32(0.1) * diag
-                npos = K // 8
-                pos = torch.stack(x[:3], 1)[:npos].cpu().numpy()
-                nrm = torch.stack(nr, 1)[:npos].cpu().numpy()
-                m.init_hemisphere(pos, nrm, 0.01, 3.0 * float(diag) / npos, 0x1A17 + v)
-                mix[v] = m
-            m = mix[v]
-            its.append(1 if async_ else (2 if m.get_state()["scalars"][3] < 4 else 1))
-            mixes.append(m)
-            for i in range(6):
-                xs[i].append(x[i])
-            ws.append(w)
-            segs.append(segs[-1] + int(w.numel()))
-        samples = pkg.DeviceSamples([torch.cat(t) for t in xs], torch.cat(ws))
-        pkg.em_step_batched_iters(mixes, samples, np.asarray(segs, np.int64), np.asarray(its, np.int32))
-        torch.cuda.synchronize()
-        pending[:] = ready
+        loop.push(from_device(out))
+        loop.update()
+        loop.optimize(spp)
+    if state is not None:
+        state["loop"] = loop
     if async_:
         if state is not None:
-            state["update"] = update
-            state["cond"] = cond
-        return [cond.get(i) for i in range(nn())]
-    return [mix.get(i) for i in range(nn())]
+            state["update"] = loop.update
+            state["cond"] = loop.cond
+        return loop.table()
+    return loop.mixtures()
 
 
 def test_mixed_wavefront_equals_separate_calls(pkg, scenes, gpu):
@@ -401,23 +294,6 @@ def test_native_guiding_model_equals_host_loop(pkg, scenes, gpu, plog, K):
     # (the fallback counts may differ: per-node routing to the full-K path
     # depends on each tree's own history of guided launches, never the results)
     plog(f"guided_render_fallback_fraction_K{K}", st_g["fallback_queries"] / max(1, st_g["guided_queries"]), 1.0)
-
-
-def _assert_same_mixtures(ref, got):
-    assert len(got) == len(ref)
-    n = 0
-    for i, (r, m) in enumerate(zip(ref, got)):
-        assert (r is None) == (m is None), i
-        if r is None:
-            continue
-        n += 1
-        pr, pm = r.get_params(), m.get_params()
-        for k in ("weights", "mean", "cov", "cholLInv", "detInv", "cdf"):
-            np.testing.assert_array_equal(pr[k], pm[k], err_msg=f"node {i} {k}")
-        sr, sm = r.get_state(), m.get_state()
-        for k in sr:
-            np.testing.assert_array_equal(sr[k], sm[k], err_msg=f"node {i} state {k}")
-    return n
 
 
 def test_native_guiding_model_async_equals_host_loop(pkg, scenes, gpu, plog):

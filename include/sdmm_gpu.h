@@ -1081,6 +1081,79 @@ int sdmm_guiding_iteration(sdmm_guiding* g, sdmm_scene* scene, const sdmm_li_par
  * mean) and iteration_sqr%05i.exr (its mean of squares) per render pass. */
 int sdmm_write_exr(const char* path, int width, int height, const float* rgb, int spp, int iteration, float time);
 
+/* The reader of what sdmm_write_exr writes (the reference reads its dumps with
+ * pyexr: scripts/combine_renders.py:44-51): a single-part scanline file,
+ * uncompressed, FLOAT channels among which R, G and B, listed in any order,
+ * into HOST planes rgb[3][height][width] (R, G, B); rgb NULL: a size query.
+ * *spp, *iteration, *time (each nullable) take the attributes of those names,
+ * 0 / 0 / 0.0f where the file has none.  Anything else is SDMM_E_INVALID with
+ * a message: a compression, a HALF or UINT channel, tiles, a missing channel,
+ * a truncated file, a line offset or a data window pointing outside the file,
+ * more than 2^26 pixels.  Every offset is checked before it is followed. */
+int sdmm_read_exr(const char* path, int* width, int* height, float* rgb, int* spp, int* iteration, float* time);
+
+/* ---- film: a run's passes combined by inverse variance, and its errors -----
+ * The reference integrator composes no final image; its results come from
+ * scripts/combine_renders.py and scripts/test_suite_utils.py run over the
+ * dumped passes.  The film is that stage, fed straight from the planes
+ * sdmm_li_render / sdmm_guiding_iteration write ("Film"; the
+ * arithmetic: csrc/film.h).
+ *
+ * device >= 0: a device film; every image pointer is a device block of planes
+ * [3][height * width] and work is enqueued on the call's hip_stream.  Calls on
+ * one film must be ordered by the caller (one stream, or events).
+ * device = -1: a host film; the same code on the CPU over host pointers,
+ * hip_stream ignored, no HIP call: it runs on a machine without a GPU and its
+ * results are bitwise the device film's (NaN payloads aside).
+ *
+ * Validation (SDMM_E_INVALID with a message): NULL handles and pointers, width
+ * or height < 1 or more than 2^26 pixels, an unknown mode, first_iteration < 0,
+ * spp < 2 (the variance divides by spp - 1). */
+typedef struct sdmm_film sdmm_film;
+enum {
+    SDMM_FILM_VAR = 0,       /* 'var' (the default of combine_renders.py:167): weight = per-channel variance */
+    SDMM_FILM_MAX_VAR = 1,   /* 'max_var': max(pixel variance, per-channel variance), NaN kept */
+    SDMM_FILM_UNIFORM = 2    /* 'uniform': 1 / spp */
+};
+typedef struct {
+    double pcv[3];               /* per_channel_variance (:220), an fp64 mean */
+    double mean_pixel_variance;  /* var_data (:229), stats.json's mean_pixel_variance */
+    int included;                /* iteration >= first_iteration (:230) */
+} sdmm_film_stats;
+typedef struct {
+    double mrse, mape, smape;    /* test_suite_utils.py:148-155 under aggregate (:116-118) */
+} sdmm_film_error;
+/* first_iteration: the first pass that enters the estimate (the reference: 4). */
+int sdmm_film_create(int width, int height, int mode, int first_iteration, int device, sdmm_film** out);
+void sdmm_film_destroy(sdmm_film* f);
+/* One pass (combine_renders.py:206-242): its variance statistics, and, when
+ * included, final += image / w and recip += 1 / w.  image / image_sqr: the
+ * pass's mean and mean of squares.  pass_stats NULL: a device film returns
+ * with the work in flight (no host synchronisation); otherwise the stream is
+ * synchronised and *pass_stats filled. */
+int sdmm_film_add_pass(sdmm_film* f, const float* image, const float* image_sqr, int spp, int iteration,
+                       void* hip_stream, sdmm_film_stats* pass_stats);
+/* The history of pass statistics (host side; a device film synchronises the
+ * stream of its last pass to fetch what is still in flight).  sdmm_film_passes:
+ * the count, -1 for a NULL film. */
+int sdmm_film_passes(const sdmm_film* f);
+int sdmm_film_pass_stats(sdmm_film* f, int i, sdmm_film_stats* out);
+/* final / recip (:246) into out[3][height * width]; SDMM_E_STATE before the
+ * first included pass.  Asynchronous on hip_stream for a device film. */
+int sdmm_film_resolve(sdmm_film* f, float* out, void* hip_stream);
+/* MrSE, MAPE, SMAPE against ground_truth (:251-257): of `image`, or, image
+ * NULL, of the current combined estimate (SDMM_E_STATE before the first
+ * included pass) -- the reference's INDIVIDUAL and CUMULATIVE error types.
+ * Synchronises hip_stream. */
+int sdmm_film_errors(sdmm_film* f, const float* image, const float* ground_truth, void* hip_stream,
+                     sdmm_film_error* out);
+/* The clipped per-pixel variance of a pass (:213-219) into out[3][height *
+ * width]; changes no film state.  Asynchronous on hip_stream for a device film. */
+int sdmm_film_variance(const sdmm_film* f, const float* image, const float* image_sqr, int spp, float* out,
+                       void* hip_stream);
+/* Forget every pass (a device film synchronises the stream of its last pass). */
+int sdmm_film_reset(sdmm_film* f);
+
 const char* sdmm_last_error(void);
 int sdmm_abi_version(void);
 

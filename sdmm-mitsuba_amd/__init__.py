@@ -184,6 +184,19 @@ def lib():
         L.sdmm_li_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
         L.sdmm_write_exr.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float]
+        L.sdmm_read_exr.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float)]
+        L.sdmm_film_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.sdmm_film_destroy.argtypes = [C.c_void_p]
+        L.sdmm_film_destroy.restype = None
+        L.sdmm_film_add_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p]
+        L.sdmm_film_passes.argtypes = [C.c_void_p]
+        L.sdmm_film_pass_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.sdmm_film_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sdmm_film_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sdmm_film_variance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.sdmm_film_reset.argtypes = [C.c_void_p]
         L.sdmm_push_training.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p,
                                          C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64)]
         L.sdmm_kmeanspp_select.argtypes = [C.c_void_p, C.c_void_p * 3, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
@@ -285,6 +298,8 @@ EXPORTED_SYMBOLS = [
     "sdmm_scene_intersect", "sdmm_scene_intersect_host", "sdmm_scene_intersect_host_levels",
     "sdmm_mesh_bvh_dump",
     "sdmm_env_eval", "sdmm_env_eval_host",
+    "sdmm_read_exr", "sdmm_film_create", "sdmm_film_destroy", "sdmm_film_add_pass", "sdmm_film_passes",
+    "sdmm_film_pass_stats", "sdmm_film_resolve", "sdmm_film_errors", "sdmm_film_variance", "sdmm_film_reset",
 ]
 
 
@@ -1245,6 +1260,202 @@ def write_exr(path, rgb, spp: int = 0, iteration: int = 0, time: float = 0.0):
         raise ValueError("rgb must be (3, H, W)")
     _check(lib().sdmm_write_exr(os.fsencode(path), a.shape[2], a.shape[1], a.ctypes.data, int(spp), int(iteration),
                                 float(time)))
+
+
+def read_exr(path):
+    """What write_exr writes, back (sdmm_read_exr): (rgb (3, H, W) float32,
+    {"spp", "iteration", "time"})."""
+    w, h, spp, it, t = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_float()
+    name = os.fsencode(path)
+    _check(lib().sdmm_read_exr(name, C.byref(w), C.byref(h), None, None, None, None))
+    rgb = np.empty((3, h.value, w.value), np.float32)
+    _check(lib().sdmm_read_exr(name, C.byref(w), C.byref(h), rgb.ctypes.data, C.byref(spp), C.byref(it),
+                               C.byref(t)))
+    return rgb, {"spp": spp.value, "iteration": it.value, "time": t.value}
+
+
+class _FilmStats(C.Structure):
+    _fields_ = [("pcv", C.c_double * 3), ("mean_pixel_variance", C.c_double), ("included", C.c_int)]
+
+
+class _FilmError(C.Structure):
+    _fields_ = [("mrse", C.c_double), ("mape", C.c_double), ("smape", C.c_double)]
+
+
+FILM_MODES = {"var": 0, "max_var": 1, "uniform": 2}
+
+
+class Film:
+    """A run's passes combined by inverse variance and scored against a ground
+    truth (sdmm_film_*; scripts/combine_renders.py and test_suite_utils.py of
+    the reference).  device >= 0: a device film over (3, H, W) float32 torch
+    tensors on that device, work on the current stream (or `stream`);
+    device = -1: a host film over numpy arrays, no GPU needed."""
+
+    def __init__(self, width: int, height: int, mode="var", first_iteration: int = 4, device: int = 0):
+        h = C.c_void_p()
+        m = FILM_MODES.get(mode, mode)
+        if not isinstance(m, int):
+            raise ValueError(f"unknown film mode {mode!r}")
+        _check(lib().sdmm_film_create(int(width), int(height), m, int(first_iteration), int(device), C.byref(h)))
+        self.h, self.width, self.height, self.device, self.mode = h, int(width), int(height), int(device), mode
+
+    def __del__(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.sdmm_film_destroy(self.h)
+            self.h = None
+
+    def _in(self, a, keep):
+        """A (3, H, W) float32 plane block -> its pointer (keep holds it alive)."""
+        if a is None:
+            return None
+        shape = (3, self.height, self.width)
+        if self.device < 0:
+            a = np.ascontiguousarray(a, np.float32)
+            if a.size != 3 * self.height * self.width:
+                raise ValueError(f"expected {shape}, got {a.shape}")
+            keep.append(a)
+            return C.c_void_p(a.ctypes.data)
+        import torch
+        if not (a.is_cuda and a.dtype == torch.float32 and a.numel() == 3 * self.height * self.width):
+            raise ValueError(f"expected a float32 device tensor {shape}")
+        if (a.device.index or 0) != self.device:
+            raise ValueError("tensor on another device than the film")
+        a = a.contiguous()
+        keep.append(a)
+        return C.c_void_p(a.data_ptr())
+
+    def _out(self):
+        if self.device < 0:
+            return np.empty((3, self.height, self.width), np.float32)
+        import torch
+        return torch.empty(3, self.height, self.width, device=torch.device("cuda", self.device))
+
+    def _ptr(self, a):
+        return C.c_void_p(a.ctypes.data if self.device < 0 else a.data_ptr())
+
+    def _stream(self, stream):
+        if self.device < 0:
+            return None
+        import torch
+        return C.c_void_p(stream if stream is not None
+                          else torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+
+    def _hold(self, keep, stream):
+        """Inputs read by work in flight on a caller's stream: the allocator
+        must not hand their memory out again before that work."""
+        if self.device >= 0 and stream:
+            import torch
+            s = torch.cuda.ExternalStream(stream)
+            for a in keep:
+                a.record_stream(s)
+
+    @staticmethod
+    def _stats(st):
+        return {"pcv": np.array(st.pcv[:], np.float64), "mean_pixel_variance": float(st.mean_pixel_variance),
+                "included": bool(st.included)}
+
+    def add_pass(self, image, image_sqr, spp: int, iteration: int, stream=None, sync: bool = True):
+        """One pass's mean and mean-of-squares images.  sync: wait and return
+        its statistics; sync=False (a device film) leaves the work in flight,
+        the statistics stay available from pass_stats()."""
+        keep = []
+        st = _FilmStats()
+        _check(lib().sdmm_film_add_pass(self.h, self._in(image, keep), self._in(image_sqr, keep), int(spp),
+                                        int(iteration), self._stream(stream), C.byref(st) if sync else None))
+        self._hold(keep, stream)
+        return self._stats(st) if sync else None
+
+    def __len__(self):
+        return int(lib().sdmm_film_passes(self.h))
+
+    def pass_stats(self, i: int):
+        st = _FilmStats()
+        _check(lib().sdmm_film_pass_stats(self.h, int(i), C.byref(st)))
+        return self._stats(st)
+
+    def resolve(self, out=None, stream=None):
+        """The combined estimate final / recip, (3, H, W)."""
+        out = self._out() if out is None else out
+        _check(lib().sdmm_film_resolve(self.h, self._ptr(out), self._stream(stream)))
+        return out
+
+    def errors(self, ground_truth, image=None, stream=None):
+        """{"MrSE", "MAPE", "SMAPE"} of `image`, or of the combined estimate."""
+        keep = []
+        e = _FilmError()
+        _check(lib().sdmm_film_errors(self.h, self._in(image, keep), self._in(ground_truth, keep),
+                                      self._stream(stream), C.byref(e)))
+        return {"MrSE": e.mrse, "MAPE": e.mape, "SMAPE": e.smape}
+
+    def variance(self, image, image_sqr, spp: int, out=None, stream=None):
+        """The clipped per-pixel variance of a pass, (3, H, W); no film state."""
+        keep = []
+        out = self._out() if out is None else out
+        _check(lib().sdmm_film_variance(self.h, self._in(image, keep), self._in(image_sqr, keep), int(spp),
+                                        self._ptr(out), self._stream(stream)))
+        self._hold(keep, stream)
+        return out
+
+    def reset(self):
+        _check(lib().sdmm_film_reset(self.h))
+
+
+def combine_run(run_dir, mode="var", ground_truth=None, out=None, first_iteration: int = 4, device: int = -1):
+    """combine_renders.py's combine_renders over a run directory: the passes
+    iteration%05i.exr / iteration_sqr%05i.exr (listed and paired as :173-183,
+    :199-204 do) go through a film; the combined image is written to `out`
+    (default run_dir/combined.exr) once a pass was included; where stats.json
+    exists its rows get mean_pixel_variance and ttuv (:266-277).  Returns
+    {"mean_pixel_variance": [...], "included": [...], "out": path or None} and,
+    with a ground truth (a path or a (3, H, W) array), the per-pass "MrSE",
+    "MAPE", "SMAPE" lists: of the combined estimate once there is one, of the
+    pass's own image before (the reference's CUMULATIVE error type)."""
+    import json
+    import re
+    run_dir = Path(run_dir)
+    names = sorted(os.listdir(run_dir))
+    images = [n for n in names if re.search(r"^iteration[0-9]*\.exr$", n)]
+    squares = [n for n in names if re.search(r"^iteration_sqr[0-9]*\.exr$", n)]
+    gt = ground_truth
+    if isinstance(gt, (str, os.PathLike)):
+        gt = read_exr(gt)[0]
+    res = {"mean_pixel_variance": [], "included": [], "out": None}
+    if gt is not None:
+        res.update({"MrSE": [], "MAPE": [], "SMAPE": []})
+    film = None
+    for a, b in zip(images, squares):
+        iteration = int(re.search(r"^iteration([0-9]*)\.exr$", a).group(1))
+        img, attrs = read_exr(run_dir / a)
+        sqr, _ = read_exr(run_dir / b)
+        if film is None:
+            film = Film(img.shape[2], img.shape[1], mode, first_iteration, device)
+            if device >= 0 and gt is not None:
+                import torch
+                gt = torch.from_numpy(np.ascontiguousarray(gt, np.float32)).to(torch.device("cuda", device))
+        if device >= 0:
+            import torch
+            img, sqr = (torch.from_numpy(x).to(torch.device("cuda", device)) for x in (img, sqr))
+        st = film.add_pass(img, sqr, attrs["spp"], iteration)
+        res["mean_pixel_variance"].append(st["mean_pixel_variance"])
+        res["included"].append(st["included"])
+        if gt is not None:
+            seen = any(res["included"])
+            e = film.errors(gt, None if seen else img)
+            for k in ("MrSE", "MAPE", "SMAPE"):
+                res[k].append(e[k])
+    if film is not None and any(res["included"]):
+        final = film.resolve()
+        res["out"] = str(out if out is not None else run_dir / "combined.exr")
+        write_exr(res["out"], final)
+    stats = run_dir / "stats.json"
+    if stats.exists():
+        rows = json.loads(stats.read_text())
+        for row, v in zip(rows, res["mean_pixel_variance"]):
+            row["mean_pixel_variance"] = float(v)
+            row["ttuv"] = float(v) * row["elapsed_seconds"]
+        stats.write_text(json.dumps(rows, sort_keys=True, indent=4))
+    return res
 
 
 class _TrainingOut(C.Structure):

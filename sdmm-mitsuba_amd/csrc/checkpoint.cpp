@@ -22,6 +22,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <new>
 #include <string>
 #include <string_view>
 #include <vector>
@@ -733,6 +734,160 @@ int sdmm_write_exr(const char* path, int width, int height, const float* rgb, in
     }
     ok = (std::fclose(f) == 0) && ok;
     return ok ? SDMM_OK : err(SDMM_E_INVALID, std::string("sdmm_write_exr: write failed: ") + path);
+}
+
+// The reader of the files above.  The whole file is read into memory and every
+// position is checked against its length before it is used: `at` never passes
+// `len`, and a length taken from the file is compared as `len - at`, never
+// added to `at` first.
+int sdmm_read_exr(const char* path, int* width, int* height, float* rgb, int* spp, int* iteration, float* time) {
+    if (!path || !width || !height) return err(SDMM_E_INVALID, "sdmm_read_exr: invalid argument");
+    const std::string who = std::string("sdmm_read_exr: ") + path + ": ";
+    auto bad = [&](const char* what) { return err(SDMM_E_INVALID, who + what); };
+    constexpr uint64_t kMaxPixels = (uint64_t)1 << 26;
+    constexpr uint64_t kMaxChannels = 8;
+    // at most: 2^26 pixels of kMaxChannels floats, their line table and headers, and a header
+    constexpr uint64_t kMaxFile = kMaxPixels * 4 * kMaxChannels + kMaxPixels * 16 + ((uint64_t)1 << 20);
+    std::vector<unsigned char> buf;
+    {
+        FILE* fp = std::fopen(path, "rb");
+        if (!fp) return bad("cannot open");
+        bool ok = std::fseek(fp, 0, SEEK_END) == 0;
+        const long size = ok ? std::ftell(fp) : -1;
+        ok = ok && size >= 0 && (uint64_t)size <= kMaxFile && std::fseek(fp, 0, SEEK_SET) == 0;
+        if (ok) {
+            try {
+                buf.resize((size_t)size);
+            } catch (const std::bad_alloc&) {
+                std::fclose(fp);
+                return err(SDMM_E_NOMEM, "out of host memory");
+            }
+            ok = size == 0 || std::fread(buf.data(), 1, (size_t)size, fp) == (size_t)size;
+        }
+        std::fclose(fp);
+        if (!ok) return bad("cannot read (or larger than any file this reader accepts)");
+    }
+    const unsigned char* d = buf.data();
+    const uint64_t len = buf.size();
+    uint64_t at = 0;
+    auto u32 = [&](uint64_t p) { uint32_t v; std::memcpy(&v, d + p, 4); return v; };
+    auto i32 = [&](uint64_t p) { int32_t v; std::memcpy(&v, d + p, 4); return v; };
+    // a NUL-terminated name of 1..255 bytes at `p`, inside [p, end): its length, or 0
+    auto cstr = [&](uint64_t p, uint64_t end) -> uint64_t {
+        uint64_t n = 0;
+        while (p + n < end && d[p + n] != 0 && n <= 255) ++n;
+        return (p + n < end && d[p + n] == 0 && n >= 1 && n <= 255) ? n : 0;
+    };
+    if (len < 8) return bad("truncated before the version field");
+    if (u32(0) != 20000630u) return bad("not an OpenEXR file");
+    const uint32_t version = u32(4);
+    if ((version & 0xFFu) != 2u) return bad("not OpenEXR version 2");
+    if (version & 0x200u) return bad("a tiled file");
+    if (version & ~(uint32_t)0x4FFu) return bad("a multi-part or deep file");   // 0x400: long names, harmless
+    at = 8;
+
+    struct Channel { std::string name; };
+    std::vector<Channel> channels;
+    int ci[3] = {-1, -1, -1};
+    bool has_channels = false, has_compression = false, has_window = false;
+    int32_t box[4] = {0, 0, 0, 0};
+    int a_spp = 0, a_iteration = 0;
+    float a_time = 0.0f;
+    for (;;) {
+        if (at >= len) return bad("truncated in the header");
+        if (d[at] == 0) {
+            ++at;
+            break;
+        }
+        const uint64_t nlen = cstr(at, len);
+        if (!nlen) return bad("a bad attribute name (or truncated in the header)");
+        const std::string name((const char*)d + at, (size_t)nlen);
+        at += nlen + 1;
+        const uint64_t tlen = cstr(at, len);
+        if (!tlen) return bad("a bad attribute type (or truncated in the header)");
+        const std::string type((const char*)d + at, (size_t)tlen);
+        at += tlen + 1;
+        if (len - at < 4) return bad("truncated in the header");
+        const int32_t size = i32(at);
+        at += 4;
+        if (size < 0 || len - at < (uint64_t)size) return bad("an attribute longer than the file");
+        const uint64_t v0 = at, v1 = at + (uint64_t)size;
+        at = v1;
+        if (name == "channels") {
+            if (type != "chlist" || has_channels) return bad("a bad channels attribute");
+            has_channels = true;
+            uint64_t q = v0;
+            for (;;) {
+                if (q >= v1) return bad("a channel list without its end");
+                if (d[q] == 0) break;
+                const uint64_t cl = cstr(q, v1);
+                if (!cl) return bad("a bad channel name");
+                const std::string cname((const char*)d + q, (size_t)cl);
+                q += cl + 1;
+                if (v1 - q < 16) return bad("a truncated channel list");
+                const int32_t ptype = i32(q), xs = i32(q + 8), ys = i32(q + 12);
+                q += 16;
+                if (ptype == 1) return bad("a HALF channel (FLOAT only)");
+                if (ptype != 2) return bad("a UINT or unknown channel type (FLOAT only)");
+                if (xs != 1 || ys != 1) return bad("a subsampled channel");
+                if (channels.size() >= kMaxChannels) return bad("more than 8 channels");
+                for (int c = 0; c < 3; ++c)
+                    if (cname == (c == 0 ? "R" : c == 1 ? "G" : "B")) {
+                        if (ci[c] >= 0) return bad("a channel listed twice");
+                        ci[c] = (int)channels.size();
+                    }
+                channels.push_back({cname});
+            }
+        } else if (name == "compression") {
+            if (type != "compression" || size != 1) return bad("a bad compression attribute");
+            if (d[v0] != 0) return bad("a compressed file (uncompressed only)");
+            has_compression = true;
+        } else if (name == "dataWindow") {
+            if (type != "box2i" || size != 16) return bad("a bad dataWindow attribute");
+            for (int i = 0; i < 4; ++i) box[i] = i32(v0 + 4 * (uint64_t)i);
+            has_window = true;
+        } else if (name == "lineOrder") {
+            if (type != "lineOrder" || size != 1 || d[v0] > 1) return bad("a bad lineOrder attribute");
+        } else if (name == "tiles") {
+            return bad("a tiled file");
+        } else if (name == "spp" && type == "int" && size == 4) {
+            a_spp = i32(v0);
+        } else if (name == "iteration" && type == "int" && size == 4) {
+            a_iteration = i32(v0);
+        } else if (name == "time" && type == "float" && size == 4) {
+            std::memcpy(&a_time, d + v0, 4);
+        }
+    }
+    if (!has_channels || !has_compression || !has_window)
+        return bad("no channels, compression or dataWindow attribute");
+    if (ci[0] < 0 || ci[1] < 0 || ci[2] < 0) return bad("a missing R, G or B channel");
+    if (box[2] < box[0] || box[3] < box[1]) return bad("a negative data window");
+    const uint64_t w = (uint64_t)((int64_t)box[2] - box[0] + 1), h = (uint64_t)((int64_t)box[3] - box[1] + 1);
+    if (w > kMaxPixels || h > kMaxPixels || w * h > kMaxPixels) return bad("more than 2^26 pixels");
+    *width = (int)w;
+    *height = (int)h;
+    if (spp) *spp = a_spp;
+    if (iteration) *iteration = a_iteration;
+    if (time) *time = a_time;
+    if (!rgb) return SDMM_OK;
+
+    if ((len - at) / 8 < h) return bad("truncated in the line offset table");
+    const uint64_t table = at, body = at + 8 * h;
+    const uint64_t line_bytes = 4 * w * (uint64_t)channels.size();   // <= 2^28 * 8
+    std::vector<bool> seen((size_t)h, false);
+    for (uint64_t i = 0; i < h; ++i) {
+        uint64_t off;
+        std::memcpy(&off, d + table + 8 * i, 8);
+        if (off < body || off > len || len - off < 8 || len - off - 8 < line_bytes)
+            return bad("a line offset outside the file (or a truncated scanline)");
+        const int64_t y = (int64_t)i32(off) - box[1];
+        if (y < 0 || (uint64_t)y >= h || seen[(size_t)y]) return bad("a scanline outside the data window, or twice");
+        if (i32(off + 4) < 0 || (uint64_t)i32(off + 4) != line_bytes) return bad("a scanline of the wrong size");
+        seen[(size_t)y] = true;
+        for (int c = 0; c < 3; ++c)
+            std::memcpy(rgb + ((uint64_t)c * h + (uint64_t)y) * w, d + off + 8 + 4 * w * (uint64_t)ci[c], (size_t)(4 * w));
+    }
+    return SDMM_OK;
 }
 
 }  // extern "C"

@@ -1,9 +1,10 @@
-// render_launch.h -- the host-callable functions render.hip defines for other
-// translation units, declared once (see launch.h).
+// render_launch.h -- the host-callable functions render.hip and film.hip define
+// for other translation units, declared once (see launch.h).
 #pragma once
 
 #include "sdmm_device.h"
 #include "render_device.h"
+#include "film.h"
 
 namespace sdmm {
 
@@ -41,5 +42,21 @@ hipError_t launch_produce_records(const STNodeDev* nodes, int num_nodes, int key
                                   void* temp, size_t temp_bytes, int64_t* seg_dev, int* lost, float* const x[6],
                                   float* const nrm[3], float* w, uint8_t* stats, int32_t* node, int64_t* source,
                                   hipStream_t st);
+
+// ---- film.hip --------------------------------------------------------------
+// scratch of a film's reductions, in doubles: which = 0 the chunk partials
+// (p0), 1 the next level (p1); sized for the nine rows of the error sums
+size_t film_partials_doubles(int64_t npix, int which);
+// the pass's variance sums -> f.rec / f.hist (and f.recip3), two launches
+hipError_t launch_film_var_reduce(const FilmPassDev& p, double* p0, double* p1, const FilmFinishDev& f,
+                                  hipStream_t st);
+// final (+)= img / w; rec: the device record launch_film_var_reduce wrote
+hipError_t launch_film_accumulate(const FilmPassDev& p, int mode, const double* rec, float wu, int first,
+                                  float* final_, float* recip_plane, hipStream_t st);
+hipError_t launch_film_resolve(const float* final_, const FilmRecip& r, int64_t npix, float* out, hipStream_t st);
+// image NULL: the combined estimate final_ / r
+hipError_t launch_film_errors(const float* image, const float* final_, const FilmRecip& r, const float* truth,
+                              int64_t npix, double* p0, double* p1, const FilmFinishDev& f, hipStream_t st);
+hipError_t launch_film_variance(const FilmPassDev& p, float* out, hipStream_t st);
 
 }  // namespace sdmm

@@ -646,6 +646,13 @@ public:
         rows_.push_back({iteration, elapsed_seconds, total_elapsed_seconds, mean_path_length, spp, total_spp});
     }
     size_t size() const { return rows_.size(); }
+    // combine_renders.py:270: the row's mean_pixel_variance (Film::add_pass's
+    // statistics); the key is written for the rows it was set on only
+    void set_mean_pixel_variance(size_t row, double v) {
+        if (row >= rows_.size()) throw Error(SDMM_E_INVALID, "RunStats::set_mean_pixel_variance: no such row");
+        rows_[row].has_variance = true;
+        rows_[row].mean_pixel_variance = v;
+    }
     void write(const std::string& path) const {   // std::setw(4) layout, keys sorted like nlohmann's
         std::string s = "[";
         for (size_t i = 0; i < rows_.size(); ++i) {
@@ -654,6 +661,7 @@ public:
             s += "        \"elapsed_seconds\": " + detail::num(r.elapsed) + ",\n";
             s += "        \"iteration\": " + std::to_string(r.iteration) + ",\n";
             s += "        \"mean_path_length\": " + detail::num(r.mean_path_length) + ",\n";
+            if (r.has_variance) s += "        \"mean_pixel_variance\": " + detail::num(r.mean_pixel_variance) + ",\n";
             s += "        \"spp\": " + std::to_string(r.spp) + ",\n";
             s += "        \"total_elapsed_seconds\": " + detail::num(r.total_elapsed) + ",\n";
             s += "        \"total_spp\": " + std::to_string(r.total_spp) + "\n    }";
@@ -667,8 +675,57 @@ private:
         int iteration;
         double elapsed, total_elapsed, mean_path_length;
         int spp, total_spp;
+        bool has_variance = false;
+        double mean_pixel_variance = 0.0;
     };
     std::vector<Row> rows_;
+};
+
+// The film (sdmm_film_*): a run's passes combined by inverse variance and
+// scored against a ground truth -- what scripts/combine_renders.py does over
+// the dumped passes, fed from the planes the render wrote.  device >= 0: device
+// planes [3][height * width], work on hip_stream; device = -1: a host film
+// over host planes, no GPU needed.
+class Film {
+public:
+    Film(int width, int height, int mode = SDMM_FILM_VAR, int first_iteration = 4, int device = 0) {
+        check(sdmm_film_create(width, height, mode, first_iteration, device, &h_), "sdmm_film_create");
+    }
+    ~Film() { sdmm_film_destroy(h_); }
+    Film(const Film&) = delete;
+    Film& operator=(const Film&) = delete;
+    sdmm_film* handle() { return h_; }
+    // one pass; returns its statistics (synchronises the stream)
+    sdmm_film_stats add_pass(const float* image, const float* image_sqr, int spp, int iteration,
+                             void* hip_stream = nullptr) {
+        sdmm_film_stats st{};
+        check(sdmm_film_add_pass(h_, image, image_sqr, spp, iteration, hip_stream, &st), "sdmm_film_add_pass");
+        return st;
+    }
+    // the same without waiting: the statistics stay available from pass_stats()
+    void add_pass_async(const float* image, const float* image_sqr, int spp, int iteration, void* hip_stream) {
+        check(sdmm_film_add_pass(h_, image, image_sqr, spp, iteration, hip_stream, nullptr), "sdmm_film_add_pass");
+    }
+    int passes() const { return sdmm_film_passes(h_); }
+    sdmm_film_stats pass_stats(int i) {
+        sdmm_film_stats st{};
+        check(sdmm_film_pass_stats(h_, i, &st), "sdmm_film_pass_stats");
+        return st;
+    }
+    void resolve(float* out, void* hip_stream = nullptr) { check(sdmm_film_resolve(h_, out, hip_stream), "sdmm_film_resolve"); }
+    // image NULL: the combined estimate
+    sdmm_film_error errors(const float* image, const float* ground_truth, void* hip_stream = nullptr) {
+        sdmm_film_error e{};
+        check(sdmm_film_errors(h_, image, ground_truth, hip_stream, &e), "sdmm_film_errors");
+        return e;
+    }
+    void variance(const float* image, const float* image_sqr, int spp, float* out, void* hip_stream = nullptr) const {
+        check(sdmm_film_variance(h_, image, image_sqr, spp, out, hip_stream), "sdmm_film_variance");
+    }
+    void reset() { check(sdmm_film_reset(h_), "sdmm_film_reset"); }
+
+private:
+    sdmm_film* h_ = nullptr;
 };
 
 // pdfSurface's mixing of BSDF and guiding densities (sdmm_proc.cpp:587-589):

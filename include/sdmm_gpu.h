@@ -747,6 +747,36 @@ int sdmm_bsdf_roughdielectric_host(const float* params, const float spec_trans[3
 int sdmm_bsdf_roughdielectric_device(const float* params, const float spec_trans[3], int64_t nq,
                                      const float* const wi[3], const float* const* u, float* const wo[3],
                                      float* const value[3], float* pdf, float* eta_out, void* hip_stream);
+/* The two delta-only BSDFs on the host, as the device Li runs them, with the
+ * semantics of sdmm_bsdf_roughdielectric_host; the call dispatches on
+ * params[0].  Kind 5, SmoothDielectric (bsdfs/dielectric.cpp: sample
+ * :277-333, eval :228-253, pdf :255-275; ERadiance, both components):
+ * spec_trans its specularTransmittance, wi.z < 0 a hit from inside, wi.z == 0
+ * gives 0.  Kind 6, SmoothConductor (bsdfs/conductor.cpp:223-285): one-sided
+ * (wi.z <= 0 gives 0), spec_trans not read (may be NULL).
+ * With u (2 uniforms, the reference's sample; only u[0] is read): kind 5
+ * reflects when u[0] <= F (so always at a total internal reflection, F = 1) --
+ * wo = reflect(wi), value = specularReflectance, pdf = F, *eta_out = 1 -- and
+ * transmits otherwise: wo = refract(wi, cosThetaT), value =
+ * specularTransmittance * factor^2 with factor = 1 / eta entering and eta
+ * leaving, pdf = 1 - F, *eta_out = eta entering, 1 / eta leaving.  Kind 6: wo
+ * = reflect(wi), value = specularReflectance * fresnelConductorExact(cos
+ * theta_i, eta, k), pdf 1, *eta_out 1.  A zero value comes with its lobe's wo
+ * and pdf, except for wi.z == 0 and the conductor's back side (wo = +z, pdf
+ * 0).  u NULL: wo is given and value / pdf are the reference's eval / pdf
+ * under EDiscrete -- the lobe's value times its probability (reflectance * F,
+ * transmittance * factor^2 * (1 - F), the conductor's value) and that
+ * probability where |dot(lobe direction, wo) - 1| <= DeltaEpsilon = 1e-3, 0
+ * elsewhere; *eta_out what sample sets for the lobe on wo's side.  Floats in
+ * and out, double in between, as the rough dielectric's pair. */
+int sdmm_bsdf_smooth_host(const float* params, const float spec_trans[3], const float wi[3], const float* u,
+                          float wo[3], float value[3], float* pdf, float* eta_out);
+/* The same over nq queries on device planes (SoA), asynchronous on
+ * hip_stream, each query bitwise the host call's: u[2] the uniforms' planes
+ * (sample mode; u[1] must be set and is not read) or NULL (eval mode). */
+int sdmm_bsdf_smooth_device(const float* params, const float spec_trans[3], int64_t nq, const float* const wi[3],
+                            const float* const* u, float* const wo[3], float* const value[3], float* pdf,
+                            float* eta_out, void* hip_stream);
 typedef struct {
     int n_quads;
     const float* quads;
@@ -786,7 +816,24 @@ typedef struct {
      * (sdmm_proc.cpp:765-767), and the path's relative index (Russian
      * roulette, :864) is multiplied by the index each bounce crossed -- for a
      * guide-chosen direction by what sample would have set for it (see
-     * sdmm_bsdf_roughdielectric_host). */
+     * sdmm_bsdf_roughdielectric_host).
+     * Kind 5, smooth dielectric (bsdfs/dielectric.cpp; its
+     * specularTransmittance in `reflectance`): [1..3] specularReflectance,
+     * [4] eta = intIOR / extIOR (> 0 and != 1), [5] 1 / eta, [6], [7] unused;
+     * two-sided like kind 4.  Kind 6, smooth conductor (bsdfs/conductor.cpp;
+     * `reflectance` unused): [1..3] specularReflectance, [4] eta, [5] k (a
+     * gray conductor, as kind 2), [6], [7] unused; one-sided.  Both are delta
+     * only (sdmm_bsdf_smooth_host): a bounce on one takes the BSDF's sample
+     * with pdf = bsdfPdf, queries no guide (it is not counted in
+     * guided_queries and takes no row of the product's table), saves no
+     * vertex and still advances the depth (sdmm_proc.cpp:297-302, :764);
+     * radiance found after it reaches the vertices saved before it.  The lobe
+     * choice is dimension 0 of the bounce's stream; the path's relative index
+     * takes the crossed eta as for kind 4.  A learned_models /
+     * learned_models_nd entry on such a BSDF is not read, nor validated.  Not supported on
+     * these kinds: textures, a spectral (per-channel) eta or k, the thin
+     * dielectric, and the reference's ENull passage through index-matched
+     * interfaces (eta == 1 is rejected). */
     const float* bsdf_params;
     /* nullable: n_bsdfs entries (appended in round 6) -- a rough conductor's
      * learned BSDF, the material's SDMM4 (roughconductor.cpp:182-194,

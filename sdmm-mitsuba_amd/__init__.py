@@ -223,6 +223,9 @@ def lib():
         L.sdmm_bsdf_roughdielectric_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p * 3, C.c_void_p,
                                                        C.c_void_p * 3, C.c_void_p * 3, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+        L.sdmm_bsdf_smooth_host.argtypes = [C.c_void_p] * 8
+        L.sdmm_bsdf_smooth_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p * 3, C.c_void_p,
+                                              C.c_void_p * 3, C.c_void_p * 3, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdmm_stree_publish.argtypes = [C.c_void_p, C.c_void_p]
         L.sdmm_guide_ctx_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.sdmm_guide_ctx_destroy.argtypes = [C.c_void_p]
@@ -295,6 +298,7 @@ EXPORTED_SYMBOLS = [
     "sdmm_learned_conditional", "sdmm_learned_conditional_device", "sdmm_learned_save_json",
     "sdmm_learned_load_json", "sdmm_bsdf_phong_host",
     "sdmm_bsdf_roughdielectric_host", "sdmm_bsdf_roughdielectric_device",
+    "sdmm_bsdf_smooth_host", "sdmm_bsdf_smooth_device",
     "sdmm_scene_intersect", "sdmm_scene_intersect_host", "sdmm_scene_intersect_host_levels",
     "sdmm_mesh_bvh_dump",
     "sdmm_env_eval", "sdmm_env_eval_host",
@@ -1801,6 +1805,58 @@ def bsdf_roughdielectric_device(params, spec_trans, wi, u=None, wo=None, stream=
     up = None if u is None else (C.c_void_p * 3)(*[t.data_ptr() for t in u])
     s_ = torch.cuda.current_stream(dev) if stream is None else stream
     _check(lib().sdmm_bsdf_roughdielectric_device(
+        params.ctypes.data, st.ctypes.data, nq, (C.c_void_p * 3)(*[t.data_ptr() for t in wi]),
+        None if up is None else C.cast(up, C.c_void_p), (C.c_void_p * 3)(*[t.data_ptr() for t in out]),
+        (C.c_void_p * 3)(*[t.data_ptr() for t in value]), pdf.data_ptr(), eta.data_ptr(),
+        C.c_void_p(int(s_.cuda_stream) or None)))
+    return out, value, pdf, eta
+
+
+def bsdf_smooth_host(params, spec_trans, wi, u=None, wo=None):
+    """SmoothDielectric / SmoothConductor (bsdf kinds 5 and 6, by params[0])
+    on the host (sdmm_bsdf_smooth_host), local frame: sample (u given, 2
+    uniforms of which the first is read: (wo, weight, pdf, eta)) or the
+    EDiscrete eval / pdf of a given wo ((wo, eval, pdf, eta)); eta: the
+    relative index the lobe crosses.  spec_trans: a kind-5 BSDF's
+    specularTransmittance (None for kind 6)."""
+    params = np.ascontiguousarray(params, np.float32)
+    st = np.zeros(3, np.float32) if spec_trans is None else np.ascontiguousarray(spec_trans, np.float32)
+    wi = np.ascontiguousarray(wi, np.float32)
+    out = np.zeros(3, np.float32) if wo is None else np.array(wo, np.float32)
+    uu = None if u is None else np.ascontiguousarray(u, np.float32)
+    if uu is not None and uu.size != 2:
+        raise SDMMError("u: 2 uniforms expected")
+    value = np.zeros(3, np.float32)
+    pdf, eta = C.c_float(), C.c_float()
+    _check(lib().sdmm_bsdf_smooth_host(params.ctypes.data, st.ctypes.data, wi.ctypes.data,
+                                       None if uu is None else uu.ctypes.data, out.ctypes.data, value.ctypes.data,
+                                       C.cast(C.byref(pdf), C.c_void_p), C.cast(C.byref(eta), C.c_void_p)))
+    return out, value, float(np.float32(pdf.value)), float(np.float32(eta.value))
+
+
+def bsdf_smooth_device(params, spec_trans, wi, u=None, wo=None, stream=None):
+    """sdmm_bsdf_smooth_device over device planes: wi (3 float32 tensors of
+    nq), u (2 tensors: sample mode) or wo (3 tensors: eval mode).  (wo[3],
+    value[3], pdf, eta) device tensors; each query bitwise the host call's."""
+    import torch
+    params = np.ascontiguousarray(params, np.float32)
+    st = np.zeros(3, np.float32) if spec_trans is None else np.ascontiguousarray(spec_trans, np.float32)
+    nq = wi[0].numel()
+    dev = wi[0].device
+    if (u is None) == (wo is None):
+        raise SDMMError("give either u (sample) or wo (eval)")
+    if u is not None and len(u) != 2:
+        raise SDMMError("u: 2 planes expected")
+    for t in list(wi) + list(u if u is not None else wo):
+        if t.numel() != nq or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise SDMMError("planes: contiguous float32 device tensors of one value per query")
+    out = [torch.empty(nq, device=dev) for _ in range(3)] if wo is None else list(wo)
+    value = [torch.empty(nq, device=dev) for _ in range(3)]
+    pdf = torch.empty(nq, device=dev)
+    eta = torch.empty(nq, device=dev)
+    up = None if u is None else (C.c_void_p * 2)(*[t.data_ptr() for t in u])
+    s_ = torch.cuda.current_stream(dev) if stream is None else stream
+    _check(lib().sdmm_bsdf_smooth_device(
         params.ctypes.data, st.ctypes.data, nq, (C.c_void_p * 3)(*[t.data_ptr() for t in wi]),
         None if up is None else C.cast(up, C.c_void_p), (C.c_void_p * 3)(*[t.data_ptr() for t in out]),
         (C.c_void_p * 3)(*[t.data_ptr() for t in value]), pdf.data_ptr(), eta.data_ptr(),

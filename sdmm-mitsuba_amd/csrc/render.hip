@@ -26,8 +26,9 @@
 // (plastic.cpp: a delta specular lobe with the dielectric Fresnel reflectance
 // over a diffuse base, the lobe chosen by Fresnel-weighted probability), rough
 // conductors, Phong BSDFs (bsdf_phong.h) and rough dielectrics
-// (bsdf_roughdielectric.h: the one two-sided, transmitting material), one-
-// sided area emitters (area.cpp: Le = radiance on the normal side) and an
+// (bsdf_roughdielectric.h: two-sided, transmitting), smooth dielectrics and
+// smooth conductors (bsdf_smooth.h: delta only -- such a bounce queries no
+// guide and saves no vertex), one-sided area emitters (area.cpp: Le = radiance on the normal side) and an
 // optional environment emitter (envmap.h: constant or lat-long map, seen by
 // every ray that leaves the scene).  No NEE (the plugin's
 // NEE block is compiled out, :700-734; emitterPdf = 0, MIS weight 1, :811-816).
@@ -43,6 +44,7 @@
 #include "bsdf_phong.h"
 #include "bsdf_beckmann.h"
 #include "bsdf_roughdielectric.h"
+#include "bsdf_smooth.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -141,17 +143,7 @@ __device__ __forceinline__ float plastic_prob_specular(float Fi, float ssw) {
 // form, libcore/util.cpp:739-761) times the specular reflectance.  The
 // distribution itself: bsdf_beckmann.h.
 
-__device__ __forceinline__ float fresnel_conductor(float ci, float eta, float k) {
-    const float ci2 = ci * ci, si2 = 1.0f - ci2, si4 = si2 * si2;
-    const float t1 = eta * eta - k * k - si2;
-    const float a2pb2 = sqrtf(fmaxf(0.0f, t1 * t1 + k * k * eta * eta * 4.0f));
-    const float a = sqrtf(fmaxf(0.0f, (a2pb2 + t1) * 0.5f));
-    const float term1 = a2pb2 + ci2, term2 = a * (2.0f * ci);
-    const float rs2 = (term1 - term2) / (term1 + term2);
-    const float term3 = a2pb2 * ci2 + si4, term4 = term2 * si2;
-    const float rp2 = rs2 * (term3 - term4) / (term3 + term4);
-    return 0.5f * (rp2 + rs2);
-}
+// fresnel_conductor: bsdf_smooth.h (shared with the smooth conductor)
 
 // RoughConductor::sample(bRec, pdf, sample) (roughconductor.cpp:414-462) in the
 // local frame, wi.z > 0: wo, the weight F * (D G (wi.m) / (pdf cos)) and the
@@ -168,7 +160,7 @@ __device__ __forceinline__ bool conductor_sample(const float wi[3], const float*
     const float dm = dot3(wi, m);
     for (int a = 0; a < 3; ++a) wo[a] = 2.0f * dm * m[a] - wi[a];   // reflect
     if (wo[2] <= 0.0f) return false;
-    const float fr = fresnel_conductor(dm, bp[4], bp[5]);
+    const float fr = fresnel_conductor<float>(dm, bp[4], bp[5]);
     const float g = beckmann_g1(wi, m, alpha) * beckmann_g1(wo, m, alpha);
     const float weight = beckmann_d(m, alpha) * g * dm / (mpdf * wi[2]);
     for (int ch = 0; ch < 3; ++ch) bw[ch] = fr * bp[1 + ch] * weight;
@@ -188,7 +180,7 @@ __device__ __forceinline__ float conductor_eval_pdf(const float wi[3], const flo
     normalize3(hs, H);
     const float D = beckmann_d(H, alpha);
     if (D != 0.0f) {
-        const float fr = fresnel_conductor(dot3(wi, H), bp[4], bp[5]);
+        const float fr = fresnel_conductor<float>(dot3(wi, H), bp[4], bp[5]);
         const float G = beckmann_g1(wi, H, alpha) * beckmann_g1(wo, H, alpha);
         const float model = D * G / (4.0f * wi[2]);
         for (int ch = 0; ch < 3; ++ch) f[ch] = fr * bp[1 + ch] * model;
@@ -268,7 +260,9 @@ li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) 
 // PHONG: the variant for a scene with Phong BSDFs (the three Li kernels carry
 // Phong's code only there, so the other scenes' kernels keep their registers).
 // DIEL: likewise for a scene with rough dielectrics (bsdf_roughdielectric.h):
-// two-sided hits, the transmitted lobe and the path's relative index eta.
+// two-sided hits, the transmitted lobe and the path's relative index eta; and
+// for the delta-only BSDFs of bsdf_smooth.h (kinds 5 and 6), whose bounce takes
+// the sampled direction without a guide query (sdmm_proc.cpp:297-302).
 template <bool PHONG, bool DIEL, bool MESH>
 __global__ void __launch_bounds__(256)
 li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int max_depth, int guided,
@@ -281,6 +275,7 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     if (live && max_depth >= 0 && depth >= max_depth) live = false;   // :684-685
     int q = live ? P.quad[i] : -1;
     float n[3] = {0, 0, 0}, wi[3] = {0, 0, 0};
+    bool pure_delta = false;            // a kind-5 or kind-6 hit (DIEL)
     if (live) {
         const float* qn = prim_n<MESH>(S, q);
         const int qb = prim_bsdf<MESH>(S, q);
@@ -290,16 +285,22 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         const float* bp = S.bpar ? S.bpar + kBsdfParams * qb : nullptr;
         const int kind = bp ? (int)bp[0] : kBsdfDiffuse;
         const bool zero_spec = kind == kBsdfDiffuse || (bp[1] == 0.0f && bp[2] == 0.0f && bp[3] == 0.0f);
-        const bool zero_diff = kind == kBsdfConductor || (rho[0] == 0.0f && rho[1] == 0.0f && rho[2] == 0.0f);
+        const bool zero_diff = kind == kBsdfConductor || (DIEL && kind == kBsdfSmoothConductor) ||
+                               (rho[0] == 0.0f && rho[1] == 0.0f && rho[2] == 0.0f);
         // no reflection from the back side or with zero reflectances (the
         // light's BSDF): sample and eval are 0, the path ends (:772-774)
         // (a rough dielectric is live from either side: it dies only at
-        // wi . n == 0 or with both its reflectance and transmittance zero)
+        // wi . n == 0 or with both its reflectance and transmittance zero; so
+        // is a smooth one, a smooth conductor is one-sided)
         const float cos_i = dot3(wi, n);
-        const bool side = DIEL && kind == kBsdfDielectric ? (cos_i > 0.0f || cos_i < 0.0f) : cos_i > 0.0f;
+        const bool side = DIEL && (kind == kBsdfDielectric || kind == kBsdfSmoothDielectric)
+                              ? (cos_i > 0.0f || cos_i < 0.0f)
+                              : cos_i > 0.0f;
         if (!side || (zero_diff && zero_spec)) live = false;
+        if (DIEL) pure_delta = kind == kBsdfSmoothDielectric || kind == kBsdfSmoothConductor;
     }
-    Q.live[i] = (uint8_t)((live && guided) ? 1 : 0);
+    // (a pure-delta bounce sends no query to the guided wavefront, :297-302)
+    Q.live[i] = (uint8_t)((live && guided && !pure_delta) ? 1 : 0);
     Q.slot[i] = -1;
     if (!live) {
         P.depth[i] = -1;
@@ -371,6 +372,18 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         Q.bw0[i] = bw[0]; Q.bw1[i] = bw[1]; Q.bw2[i] = bw[2];
         Q.bpdf[i] = bpdf;
         Q.beta[i] = crossed;
+    } else if (DIEL && pure_delta) {
+        // SmoothDielectric::sample / SmoothConductor::sample (bsdf_smooth.h)
+        // with sample.x = dimension 0 (sample.y, dimension 1, is not read); a
+        // void sample has weight 0
+        const float* st = S.refl + 3 * prim_bsdf<MESH>(S, q);
+        const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};
+        float bw[3], bpdf, crossed;
+        smooth_sample(wl, bp, st, rng_uniform(seed, gp, stream, 0), w, bw, &bpdf, &crossed);
+        Q.bw0[i] = bw[0]; Q.bw1[i] = bw[1]; Q.bw2[i] = bw[2];
+        Q.bpdf[i] = bpdf;
+        Q.beta[i] = crossed;
+        delta = 1;
     } else {
         cosine_hemisphere(rng_uniform(seed, gp, stream, 0), rng_uniform(seed, gp, stream, 1), w);
     }
@@ -616,6 +629,17 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
             mis_pdf = bsdf_pdf > 0.0f ? h * bsdf_pdf + (1.0f - h) * Q.pdf[j] : 0.0f;
             for (int ch = 0; ch < 3; ++ch) weight[ch] = mis_pdf == 0.0f ? 0.0f : f[ch] * (1.0f / mis_pdf);
         }
+    } else if (DIEL && bp && is_smooth_kind(bp[0])) {
+        // smooth dielectric, smooth conductor: the whole BSDF is delta -- the
+        // loop head's sample as it is (pdf = bsdfPdf, no guide query: slot -1;
+        // :297-302), no saved vertex (:764)
+        const float wi[3] = {-P.dx[i], -P.dy[i], -P.dz[i]};
+        inside = dot3(wi, n) < 0.0f;
+        wo[0] = Q.b0[i]; wo[1] = Q.b1[i]; wo[2] = Q.b2[i];
+        crossed = Q.beta[i];
+        mis_pdf = Q.bpdf[i];
+        weight[0] = Q.bw0[i]; weight[1] = Q.bw1[i]; weight[2] = Q.bw2[i];
+        cacheable = false;
     } else if (!valid) {
         // BSDF only, h = 1 (:316-323, :392-405): weight = rho, pdf = bsdfPdf
         wo[0] = Q.b0[i]; wo[1] = Q.b1[i]; wo[2] = Q.b2[i];
@@ -1069,6 +1093,42 @@ hipError_t launch_roughdielectric(const float* bp, const float st[3], int64_t nq
     hipLaunchKernelGGL(roughdielectric_kernel, grid_for(nq), dim3(256), 0, st_, A, nq, wi[0], wi[1], wi[2],
                        u ? u[0] : nullptr, u ? u[1] : nullptr, u ? u[2] : nullptr, wo[0], wo[1], wo[2], value[0],
                        value[1], value[2], pdf, eta_out);
+    return hipGetLastError();
+}
+
+// The delta-only BSDFs (bsdf_smooth.h) over a batch of local incident
+// directions (sdmm_bsdf_smooth_device): sample mode draws wo from u0 (u1 is
+// not read), eval mode (u0 null) evaluates the given wo; each query as the
+// host call
+__global__ void __launch_bounds__(256)
+smooth_kernel(DielectricArgs A, int64_t nq, const float* __restrict__ wi0, const float* __restrict__ wi1,
+              const float* __restrict__ wi2, const float* __restrict__ u0, float* wo0, float* wo1, float* wo2,
+              float* __restrict__ v0, float* __restrict__ v1, float* __restrict__ v2, float* __restrict__ pdf,
+              float* __restrict__ eta_out) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const float wi[3] = {wi0[q], wi1[q], wi2[q]};
+    float wo[3], f[3], p, e;
+    if (u0) {
+        smooth_sample(wi, A.bp, A.st, u0[q], wo, f, &p, &e);
+        wo0[q] = wo[0]; wo1[q] = wo[1]; wo2[q] = wo[2];
+    } else {
+        wo[0] = wo0[q]; wo[1] = wo1[q]; wo[2] = wo2[q];
+        p = smooth_eval_pdf(wi, wo, A.bp, A.st, f, &e);
+    }
+    v0[q] = f[0]; v1[q] = f[1]; v2[q] = f[2];
+    pdf[q] = p;
+    eta_out[q] = e;
+}
+hipError_t launch_smooth(const float* bp, const float st[3], int64_t nq, const float* const wi[3],
+                         const float* const* u, float* const wo[3], float* const value[3], float* pdf,
+                         float* eta_out, hipStream_t st_) {
+    if (nq <= 0) return hipSuccess;
+    DielectricArgs A{};
+    for (int i = 0; i < kBsdfParams; ++i) A.bp[i] = bp[i];
+    for (int i = 0; i < 3; ++i) A.st[i] = st ? st[i] : 0.0f;
+    hipLaunchKernelGGL(smooth_kernel, grid_for(nq), dim3(256), 0, st_, A, nq, wi[0], wi[1], wi[2],
+                       u ? u[0] : nullptr, wo[0], wo[1], wo[2], value[0], value[1], value[2], pdf, eta_out);
     return hipGetLastError();
 }
 

@@ -21,6 +21,7 @@
 #include "learned_bsdf.h"
 #include "bsdf_phong.h"
 #include "bsdf_roughdielectric.h"
+#include "bsdf_smooth.h"
 
 // the scene's derived quad data in plain IEEE float (no FMA contraction), as
 // the CPU restatement of Li forms it (oracle/sdmm_oracle_li.inc)
@@ -85,7 +86,7 @@ float dot3h(const float a[3], const float b[3]) { return a[0] * b[0] + a[1] * b[
 // path + query + vertex planes for P paths with V vertex slots
 int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
     if (P <= s->cap_paths && V <= s->cap_v && s->buf) return SDMM_OK;
-    const bool diel = s->S.has_dielectric != 0;   // (the eta planes: only with a rough dielectric)
+    const bool diel = s->S.has_dielectric != 0;   // (the eta planes: only with a dielectric or a kind-5 / 6 BSDF)
     const int64_t cap = std::max<int64_t>(P, s->cap_paths);
     const int cv = std::max(V, s->cap_v);
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
@@ -316,8 +317,20 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
                             (bp[0] == (float)kBsdfDielectric && bp[1] >= 0.0f && bp[2] >= 0.0f && bp[3] >= 0.0f &&
                              std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] > 0.0f && bp[4] != 1.0f &&
                              std::isfinite(bp[4]) && bp[5] > 0.0f && std::isfinite(bp[5]) && bp[6] > 0.0f &&
-                             bp[6] <= 2.0f);
+                             bp[6] <= 2.0f) ||
+                            (bp[0] == (float)kBsdfSmoothDielectric && bp[1] >= 0.0f && bp[2] >= 0.0f &&
+                             bp[3] >= 0.0f && std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] > 0.0f &&
+                             bp[4] != 1.0f && std::isfinite(bp[4]) && bp[5] > 0.0f && std::isfinite(bp[5])) ||
+                            (bp[0] == (float)kBsdfSmoothConductor && bp[1] >= 0.0f && bp[2] >= 0.0f &&
+                             bp[3] >= 0.0f && std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] > 0.0f &&
+                             std::isfinite(bp[4]) && bp[5] >= 0.0f && std::isfinite(bp[5]));
             if (!ok) return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid bsdf_params");
+            // a smooth dielectric's specularTransmittance (its reflectance row)
+            const float* tr = d->reflectance + 3 * b;
+            if (bp[0] == (float)kBsdfSmoothDielectric &&
+                !(tr[0] >= 0.0f && tr[1] >= 0.0f && tr[2] >= 0.0f && std::isfinite(tr[0] + tr[1] + tr[2])))
+                return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid bsdf_params (a smooth dielectric's "
+                                            "transmittance is negative or not finite)");
         }
     // learned models: at most kLearnedMaxComp components, finite, unit directions
     std::vector<float> lmod;
@@ -326,6 +339,8 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
         for (int b = 0; b < d->n_bsdfs; ++b) {
             const sdmm_learned_bsdf4& L = d->learned_models[b];
             if (L.M == 0) continue;
+            // (a delta-only BSDF never calls getDMM: its entry is not read, not even checked)
+            if (d->bsdf_params && is_smooth_kind(d->bsdf_params[kBsdfParams * b])) continue;
             if (L.M < 0 || L.M > kLearnedMaxComp || !L.weights || !L.means || !L.covs)
                 return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid learned model (1 <= M <= 8, arrays)");
             float* o = lmod.data() + (size_t)kLearnedStride * b;
@@ -353,6 +368,7 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
         for (int b = 0; b < d->n_bsdfs; ++b) {
             const sdmm_learned_bsdf& L = d->learned_models_nd[b];
             if (L.M == 0) continue;
+            if (d->bsdf_params && is_smooth_kind(d->bsdf_params[kBsdfParams * b])) continue;   // (as above)
             if ((L.C != 2 && L.C != 3) || L.M < 0 || L.M > kLearnedMaxComp || !L.weights || !L.means || !L.covs)
                 return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid learned model (C 2 or 3, 1 <= M <= 8, arrays)");
             const bool phong = d->bsdf_params && d->bsdf_params[kBsdfParams * b] == (float)kBsdfPhong;
@@ -489,6 +505,8 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
         for (int b = 0; b < d->n_bsdfs; ++b) {
             if (d->bsdf_params[kBsdfParams * b] == (float)kBsdfPhong) S.has_phong = 1;
             if (d->bsdf_params[kBsdfParams * b] == (float)kBsdfDielectric) S.has_dielectric = 1;
+            // (the delta-only kinds live in the DIEL kernels: no variant of their own)
+            if (is_smooth_kind(d->bsdf_params[kBsdfParams * b])) S.has_dielectric = 1;
         }
     S.rad = s->drad;
     S.env = env;
@@ -669,6 +687,39 @@ int sdmm_bsdf_roughdielectric_device(const float* params, const float spec_trans
         !value[1] || !value[2] || !pdf || !eta_out || (u && (!u[0] || !u[1] || !u[2])))
         return fail(SDMM_E_INVALID, "sdmm_bsdf_roughdielectric_device: NULL plane");
     HIP_TRY(launch_roughdielectric(params, spec_trans, nq, wi, u, wo, value, pdf, eta_out, (hipStream_t)hip_stream));
+    return SDMM_OK;
+}
+
+int sdmm_bsdf_smooth_host(const float* params, const float spec_trans[3], const float wi[3], const float* u,
+                          float wo[3], float value[3], float* pdf, float* eta_out) {
+    if (!params || !is_smooth_kind(params[0]) || (params[0] == (float)kBsdfSmoothDielectric && !spec_trans) || !wi ||
+        !wo || !value || !pdf || !eta_out)
+        return fail(SDMM_E_INVALID, "sdmm_bsdf_smooth_host: invalid argument (params of a kind-5 or kind-6 BSDF)");
+    const float none[3] = {0.0f, 0.0f, 0.0f};
+    const float* st = spec_trans ? spec_trans : none;
+    const unsigned csr = _mm_getcsr();
+    _mm_setcsr(csr | 0x8040u);
+    if (u) {
+        float o[3];
+        smooth_sample(wi, params, st, u[0], o, value, pdf, eta_out);
+        for (int a = 0; a < 3; ++a) wo[a] = o[a];
+    } else {
+        *pdf = smooth_eval_pdf(wi, wo, params, st, value, eta_out);
+    }
+    _mm_setcsr(csr);
+    return SDMM_OK;
+}
+
+int sdmm_bsdf_smooth_device(const float* params, const float spec_trans[3], int64_t nq, const float* const wi[3],
+                            const float* const* u, float* const wo[3], float* const value[3], float* pdf,
+                            float* eta_out, void* hip_stream) {
+    if (!params || !is_smooth_kind(params[0]) || (params[0] == (float)kBsdfSmoothDielectric && !spec_trans) || nq < 0)
+        return fail(SDMM_E_INVALID, "sdmm_bsdf_smooth_device: invalid argument (params of a kind-5 or kind-6 BSDF)");
+    if (nq == 0) return SDMM_OK;
+    if (!wi || !wi[0] || !wi[1] || !wi[2] || !wo || !wo[0] || !wo[1] || !wo[2] || !value || !value[0] ||
+        !value[1] || !value[2] || !pdf || !eta_out || (u && (!u[0] || !u[1])))
+        return fail(SDMM_E_INVALID, "sdmm_bsdf_smooth_device: NULL plane");
+    HIP_TRY(launch_smooth(params, spec_trans, nq, wi, u, wo, value, pdf, eta_out, (hipStream_t)hip_stream));
     return SDMM_OK;
 }
 

@@ -22,7 +22,9 @@ __host__ __device__ __forceinline__ float rng_uniform(uint64_t seed, uint64_t pa
     return (float)(uint32_t)(k >> 40) * (1.0f / 16777216.0f);
 }
 // streams: 0 camera; 1 + b bounce b (dims: 0-1 BSDF sample, 2 BSDF/guide
-// choice, 3-5 guide sample, 6 roulette, 7 a rough dielectric's lobe choice);
+// choice, 3-5 guide sample, 6 roulette, 7 a rough dielectric's lobe choice; a
+// smooth dielectric's lobe choice is dim 0, dim 1 -- the other half of the
+// reference's nextSample2D -- stays unused);
 // kJitterStream + d: vertex d's jitters
 constexpr uint32_t kJitterStream = 1024;
 
@@ -37,7 +39,7 @@ struct QuadDev {
 
 // Per-BSDF parameters beside the diffuse reflectance (kBsdfParams floats per
 // BSDF): [0] kind (0 diffuse, 1 smooth plastic, 2 rough conductor, 3 Phong, 4
-// rough dielectric).
+// rough dielectric, 5 smooth dielectric, 6 smooth conductor).
 // Plastic: [1..3] specular reflectance, [4] eta = intIOR / extIOR, [5] 1 /
 // eta^2, [6] the internal diffuse Fresnel reflectance fdrInt, [7] the
 // specular sampling weight sAvg / (dAvg + sAvg) (bsdfs/plastic.cpp:159-200).
@@ -48,12 +50,19 @@ struct QuadDev {
 // Rough dielectric: [1..3] specular reflectance, [4] eta = intIOR / extIOR,
 // [5] 1 / eta, [6] the Beckmann alpha, [7] unused; its specularTransmittance
 // in the BSDF's reflectance row (bsdfs/roughdielectric.cpp:213-241).
+// Smooth dielectric: the rough one's layout without the alpha -- [1..3]
+// specular reflectance, [4] eta, [5] 1 / eta, [6], [7] unused; its
+// specularTransmittance in the reflectance row (bsdfs/dielectric.cpp).
+// Smooth conductor: [1..3] specular reflectance, [4] eta, [5] k (gray), the
+// rest unused (bsdfs/conductor.cpp).  Both are delta only (bsdf_smooth.h).
 constexpr int kBsdfParams = 8;
 constexpr int kBsdfDiffuse = 0;
 constexpr int kBsdfPlastic = 1;
 constexpr int kBsdfConductor = 2;
 constexpr int kBsdfPhong = 3;
 constexpr int kBsdfDielectric = 4;
+constexpr int kBsdfSmoothDielectric = 5;
+constexpr int kBsdfSmoothConductor = 6;
 
 struct SceneDev {
     const QuadDev* quads;
@@ -68,7 +77,7 @@ struct SceneDev {
     int width, height;
     float smin[3], snorm;
     int has_phong;        // some BSDF is Phong: the Li kernels' PHONG variants run
-    int has_dielectric;   // some BSDF is a rough dielectric: their DIEL variants run
+    int has_dielectric;   // some BSDF is a rough dielectric, or smooth (kinds 5, 6): their DIEL variants run
     // triangle mesh (mesh_bvh.h; primitive ids n_quads + i): null / 0 without one
     const BvhNode* nodes;
     const MeshTri* tris;      // leaf order
@@ -118,7 +127,7 @@ struct PathsDev {
     float* rec;              // vertex records: rec[(f * V + v) * P + p]
     int V;
     int64_t P;
-    float* eta;              // the path's relative index (sdmm_proc.cpp:788); null without a rough dielectric
+    float* eta;              // the path's relative index (sdmm_proc.cpp:788); null without DIEL kernels
 };
 
 struct QueryDev {
@@ -148,7 +157,7 @@ struct QueryDev {
     // sampled lobe delta (1) or smooth (0), its weight (RGB) and pdf
     uint8_t* bdelta;
     float *bw0, *bw1, *bw2, *bpdf;
-    float* beta;             // a rough dielectric's sample: the index it crossed (bRec.eta); null without one
+    float* beta;             // a dielectric's sample: the index it crossed (bRec.eta); null without DIEL kernels
     // product with a rough conductor's, a Phong BSDF's or a rough
     // dielectric's learned model:
     // compact query j's lobes (weights, local means, covariances) at row

@@ -26,6 +26,9 @@ hipError_t launch_env_eval(const SceneDev& S, int64_t nq, const float* const d[3
 hipError_t launch_roughdielectric(const float* bp, const float st[3], int64_t nq, const float* const wi[3],
                                   const float* const* u, float* const wo[3], float* const value[3], float* pdf,
                                   float* eta_out, hipStream_t st_);
+hipError_t launch_smooth(const float* bp, const float st[3], int64_t nq, const float* const wi[3],
+                         const float* const* u, float* const wo[3], float* const value[3], float* pdf,
+                         float* eta_out, hipStream_t st_);
 hipError_t launch_learned4(const float* rec, int M, float alpha, int64_t nq, const float* const wl[3], int keep,
                            float* w, float* mean, float* cov, int32_t* n, hipStream_t st);
 hipError_t launch_learned_nd(int C, const float* rec, int M, const float* const* rest, const float* scal, int64_t nq,

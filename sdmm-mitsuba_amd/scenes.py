@@ -196,6 +196,29 @@ def dielectric_params(specular_rgb=(1.0, 1.0, 1.0), transmittance_rgb=(1.0, 1.0,
     return np.array([4.0, *sp, eta, inv_eta, alpha, 0.0], f32), tr
 
 
+def smooth_dielectric_params(specular_rgb=(1.0, 1.0, 1.0), transmittance_rgb=(1.0, 1.0, 1.0), int_ior=1.5046,
+                             ext_ior=1.000277):
+    """(the 8 bsdf_params floats of a smooth dielectric, its
+    specularTransmittance -- the BSDF's `reflectance` row)
+    (bsdfs/dielectric.cpp; include/sdmm_gpu.h sdmm_scene_desc): kind 5,
+    specularReflectance, eta = intIOR / extIOR (bk7 / air, the plugin's
+    defaults) and 1 / eta in float.  A delta-only BSDF: reflection with the
+    Fresnel probability, refraction otherwise.  Both spectra must lie in
+    [0, 1]."""
+    bp, tr = dielectric_params(specular_rgb, transmittance_rgb, int_ior, ext_ior, alpha=0.0)
+    bp[0] = 5.0
+    return bp, tr
+
+
+def smooth_conductor_params(specular_rgb=(1.0, 1.0, 1.0), eta=1.2, k=7.0):
+    """The 8 bsdf_params floats of a smooth conductor (bsdfs/conductor.cpp;
+    include/sdmm_gpu.h sdmm_scene_desc): kind 6, specularReflectance and a
+    gray eta / k, the convention of conductor_params (default:
+    aluminium-like).  A delta-only BSDF: a one-sided mirror tinted by
+    fresnelConductorExact."""
+    return np.array([6.0, *specular_rgb, eta, k, 0.0, 0.0], np.float32)
+
+
 LEARNED_CONDUCTOR = Path(__file__).resolve().parent / "data" / "conductor_beckmann_4c.sdmm4.json"
 
 
@@ -236,7 +259,7 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
                 phong_learned=LEARNED_PHONG, phong_specular=(0.4, 0.4, 0.4), phong_exponent=30.0, dielectric=(),
                 dielectric_learned=LEARNED_DIELECTRIC, dielectric_alpha=0.1, dielectric_ior=(1.5046, 1.000277),
                 dielectric_specular=(1.0, 1.0, 1.0), dielectric_transmittance=(1.0, 1.0, 1.0), dielectric_lift=0.0,
-                mesh=()):
+                mesh=(), glass=(), mirror=(), mirror_eta_k=(1.2, 7.0)):
     """sdmm_scene_desc fields for the Cornell Box (numpy arrays).  plastic:
     names of BSDFs (e.g. "TallBox", "ShortBox", "Floor") rendered as smooth
     plastic over their diffuse reflectance (a delta specular lobe beside a
@@ -258,7 +281,13 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
     dielectric cube by that much along y: the cubes stand on the floor, and a
     glass box's bottom face would be coplanar with it.  mesh: names of the
     cubes ("ShortBox", "TallBox") given as triangles (quads_to_triangles of
-    their faces, the description's mesh fields) instead of quads."""
+    their faces, the description's mesh fields) instead of quads.
+    glass: names rendered as smooth dielectrics (kind 5: the Pool's water and
+    glass, the Torus scene's case) with dielectric_specular / _transmittance
+    / _ior, a glass cube lifted by dielectric_lift like a rough one; mirror:
+    names rendered as smooth conductors (kind 6) tinted by their reflectance
+    like `conductor`, with the gray mirror_eta_k = (eta, k).  Neither reads a
+    learned model: their bounces are delta only."""
     names = list(_BSDFS)
     quads, bsdf, flip, emitter = [], [], [], []
     mesh_quads, mesh_bsdf = [], []
@@ -269,7 +298,7 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
         bsdf.append(names.index(name)); flip.append(int(fl)); emitter.append(-1)
     for m, name in _CUBES:
         M = _mat(m)
-        if name in dielectric:
+        if name in dielectric or name in glass:
             M[1, 3] += dielectric_lift
         for f in _cube_faces(M):
             if name in mesh:
@@ -286,8 +315,8 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
         v, t = quads_to_triangles(np.asarray(mesh_quads, np.float32))
         extra.update(mesh_vertices=v.reshape(-1), triangles=t.reshape(-1), tri_bsdf=np.asarray(mesh_bsdf, np.int32))
     refl = {n: _BSDFS[n] for n in names}
-    if plastic or conductor or phong or dielectric:
-        kinds = [set(plastic), set(conductor), set(phong), set(dielectric)]
+    if plastic or conductor or phong or dielectric or glass or mirror:
+        kinds = [set(plastic), set(conductor), set(phong), set(dielectric), set(glass), set(mirror)]
         unknown = set().union(*kinds) - set(names)
         twice = {n for n in names if sum(n in k for k in kinds) > 1}
         if unknown or twice:
@@ -303,6 +332,11 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
             elif nm in dielectric:
                 bp[i], refl[nm] = dielectric_params(dielectric_specular, dielectric_transmittance, *dielectric_ior,
                                                     alpha=dielectric_alpha)
+            elif nm in glass:
+                bp[i], refl[nm] = smooth_dielectric_params(dielectric_specular, dielectric_transmittance,
+                                                           *dielectric_ior)
+            elif nm in mirror:
+                bp[i] = smooth_conductor_params(tuple(min(1.0, 1.25 * c) for c in _BSDFS[nm]), *mirror_eta_k)
         extra["bsdf_params"] = bp.reshape(-1)
         if conductor and learned is not None:
             model = load_learned(learned)
@@ -444,7 +478,7 @@ def sky_environment(width=256, height=128, sun_dir=(0.35, 0.8, 0.45), sun_radius
             "env_world_to_local": np.linalg.inv(R).astype(np.float32).reshape(-1)}
 
 
-def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=None):
+def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=None, smooth=False):
     """The Torus configuration's stand-in (test-suite/scenes/torus/torus.xml):
     a diffuse torus (reflectance .8, .8, .4; torus_mesh(nu, nv), R 1, r 0.4,
     lying on the floor) under a rough-dielectric case of quads (alpha 0.05,
@@ -455,10 +489,17 @@ def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=Non
     room and no lamp.  None (the default): a closed room of quads with a
     ceiling lamp, the proxy from before the device Li had an environment
     emitter.  The camera follows torus.xml's framing loosely: above and in
-    front of the case, looking down at the torus."""
-    names = ["Room", "Floor", "Torus", "Glass", "Light"]
+    front of the case, looking down at the torus.
+    smooth: the materials torus.xml itself names -- the case a smooth
+    dielectric (kind 5, ior 1.5: its `dielectric`, whose alpha attribute the
+    plugin ignores; no learned model) and two metal pieces, an eighth of the
+    ring each at opposite sides of it, smooth conductors
+    (kind 6: its `conductor`) with a gray eta / k near aluminium's (1.2, 7.0);
+    the reference's spectral .spd data of the metal is not used.  The rest of
+    the torus stays diffuse.  False (the default): the scene as it was."""
+    names = ["Room", "Floor", "Torus", "Glass", "Light"] + (["Metal"] if smooth else [])
     refl = {"Room": (0.6, 0.6, 0.6), "Floor": (0.5, 0.5, 0.5), "Torus": (0.8, 0.8, 0.4), "Glass": (1.0, 1.0, 1.0),
-            "Light": (0.0, 0.0, 0.0)}
+            "Light": (0.0, 0.0, 0.0), "Metal": (0.0, 0.0, 0.0)}
     quads, bsdf, emitter = [], [], []
 
     def box(lo, hi, name, inward, skip_bottom=False):
@@ -485,11 +526,20 @@ def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=Non
     if glass:
         # the case stands 0.02 above the floor: its bottom face is not coplanar with it
         box((-1.7, 0.02, -1.7), (1.7, 1.2, 1.7), "Glass", inward=False)
-        bp[names.index("Glass")], refl["Glass"] = dielectric_params(int_ior=1.5, ext_ior=1.0, alpha=0.05)
-        model = load_learned_nd(LEARNED_DIELECTRIC)
-        extra["learned_models_nd"] = [model if nm == "Glass" else None for nm in names]
+        if smooth:
+            bp[names.index("Glass")], refl["Glass"] = smooth_dielectric_params(int_ior=1.5, ext_ior=1.0)
+        else:
+            bp[names.index("Glass")], refl["Glass"] = dielectric_params(int_ior=1.5, ext_ior=1.0, alpha=0.05)
+            model = load_learned_nd(LEARNED_DIELECTRIC)
+            extra["learned_models_nd"] = [model if nm == "Glass" else None for nm in names]
     T = np.array([[1.0, 0, 0, 0], [0, 1.0, 0, 0.45], [0, 0, 1.0, 0]])
     verts, tris = torus_mesh(nu, nv, 1.0, 0.4, to_world=T)
+    tri_bsdf = np.full(len(tris), names.index("Torus"), np.int32)
+    if smooth:
+        # torus_mesh orders its triangles by the ring index: two opposite arcs of an eighth of the ring each
+        bp[names.index("Metal")] = smooth_conductor_params()
+        ring = np.arange(len(tris)) // (2 * nv)
+        tri_bsdf[((ring % (nu // 2)) < max(1, nu // 8))] = names.index("Metal")
     if environment is not None:
         extra.update(extra_env)
     return {**extra,
@@ -501,7 +551,7 @@ def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=Non
         "radiance": np.asarray([12.0, 12.0, 12.0], np.float32),
         "mesh_vertices": verts.reshape(-1),
         "triangles": tris.reshape(-1),
-        "tri_bsdf": np.full(len(tris), names.index("Torus"), np.int32),
+        "tri_bsdf": tri_bsdf,
         "camera_to_world": _look_at((0.0, 3.2, 3.6), (0.0, 0.4, 0.0), (0.0, 1.0, 0.0)),
         "fov_x_deg": 45.0,
         "near_clip": 1e-2,

@@ -917,6 +917,36 @@ typedef struct {
     const float* env_pixels;
     float env_scale;
     float env_world_to_local[9];
+    /* nullable: n_bsdfs entries, 0 or 1 (appended after env_world_to_local;
+     * the zero-initialise rule below covers older callers: NULL or all zeros
+     * and every rule above holds).  1 on BSDF b: b is the single-child
+     * <bsdf type="twosided"> (bsdfs/twosided.cpp, m_nestedBRDF[1] =
+     * m_nestedBRDF[0], :90-91) around the BSDF its row describes.  A hit with
+     * wi . n < 0 on such a BSDF (n the stored face normal, Frame(n) = (s, t,
+     * n)) is live: the bounce runs in the frame (s, t, -n) -- local wi =
+     * (wi.s, wi.t, -(wi.n)), the nested BSDF's sample, eval and pdf on it
+     * unchanged, a local w to world as s w0 + t w1 - n w2 (wi.z *= -1 ...
+     * wo.z *= -1, :111-137, :191-213; not Frame(-n), whose tangents differ),
+     * a guide-chosen direction evaluated the same way; getEta() = 1 (:244),
+     * so the path's relative index is untouched; the saved vertex carries -n
+     * (sdmm_proc.cpp:765-767).  With sample_product the learned model is
+     * conditioned on the flipped local wi and the query's frame is F = [s t
+     * -n], which is getDMM's negated column 2 of `to` and mean.z (:151-159)
+     * under the integrator's [s t n] (sdmm_proc.cpp:344-354); a diffuse row
+     * sees the flipped normal as F's third column (:306-308, :335-339); kind 1
+     * has no getDMM and keeps the plain conditional.  wi . n == 0 and zero
+     * reflectances end the path as before; kind 6 stays delta only (no query,
+     * no vertex, the depth advances), now from both sides; a front hit is
+     * bitwise what it is without the flag; an area emitter stays one-sided
+     * whatever its primitive's BSDF (emitters/area.cpp).
+     * SDMM_E_INVALID (with a message): an entry other than 0 or 1; a 1 on a
+     * kind-4 or kind-5 BSDF ("Only materials without a transmission component
+     * can be nested", :106-108).
+     * Not supported: the two-child form (m_nestedBRDF[1] != [0]; there getDMM
+     * always asks child 0, :146), vertex and shading normals, textures,
+     * two-sided emitters; the Mitsuba plugin does not run the device Li, so
+     * it takes no such flag. */
+    const int32_t* bsdf_twosided;
 } sdmm_scene_desc;
 /* The descriptor has grown across ABI revisions (bsdf_params was appended):
  * zero-initialise it (`sdmm_scene_desc d = {0};` / `memset`) before filling

@@ -1478,7 +1478,7 @@ class _SceneDesc(C.Structure):
                 ("tri_flip_normals", C.c_void_p),
                 ("env_kind", C.c_int), ("env_radiance", C.c_float * 3), ("env_width", C.c_int),
                 ("env_height", C.c_int), ("env_pixels", C.c_void_p), ("env_scale", C.c_float),
-                ("env_world_to_local", C.c_float * 9)]
+                ("env_world_to_local", C.c_float * 9), ("bsdf_twosided", C.c_void_p)]
 
 
 def _fill_geometry(d, desc, keep):
@@ -1510,6 +1510,13 @@ def _fill_geometry(d, desc, keep):
     for key in ("tri_bsdf", "tri_emitter", "tri_flip_normals"):
         if desc.get(key) is not None:
             setattr(d, key, arr(key, np.int32).ctypes.data)
+    # per BSDF: 1 = under the twosided adapter (and the kind, which the flag's validation reads)
+    if desc.get("bsdf_twosided") is not None:
+        if np.asarray(desc["bsdf_twosided"]).size != d.n_bsdfs:
+            raise SDMMError("bsdf_twosided: one entry per BSDF")
+        d.bsdf_twosided = arr("bsdf_twosided", np.int32).ctypes.data
+        if desc.get("bsdf_params") is not None:
+            d.bsdf_params = arr("bsdf_params", np.float32).ctypes.data
     _fill_env(d, desc, keep)
 
 

@@ -28,7 +28,12 @@
 // conductors, Phong BSDFs (bsdf_phong.h) and rough dielectrics
 // (bsdf_roughdielectric.h: two-sided, transmitting), smooth dielectrics and
 // smooth conductors (bsdf_smooth.h: delta only -- such a bounce queries no
-// guide and saves no vertex), one-sided area emitters (area.cpp: Le = radiance on the normal side) and an
+// guide and saves no vertex), each non-transmitting kind optionally under the
+// single-child twosided adapter (twosided.cpp, SceneDev::twosided: a hit from
+// behind runs the nested BSDF in (s, t, -n) of Frame(n), saves -n with its
+// vertex and hands the product F = [s t -n]; the two-child form, vertex and
+// shading normals, textures and two-sided emitters are not done),
+// one-sided area emitters (area.cpp: Le = radiance on the normal side) and an
 // optional environment emitter (envmap.h: constant or lat-long map, seen by
 // every ray that leaves the scene).  No NEE (the plugin's
 // NEE block is compiled out, :700-734; emitterPdf = 0, MIS weight 1, :811-816).
@@ -276,6 +281,7 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     int q = live ? P.quad[i] : -1;
     float n[3] = {0, 0, 0}, wi[3] = {0, 0, 0};
     bool pure_delta = false;            // a kind-5 or kind-6 hit (DIEL)
+    bool back = false;                  // a two-sided BSDF met from behind
     if (live) {
         const float* qn = prim_n<MESH>(S, q);
         const int qb = prim_bsdf<MESH>(S, q);
@@ -291,11 +297,13 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         // light's BSDF): sample and eval are 0, the path ends (:772-774)
         // (a rough dielectric is live from either side: it dies only at
         // wi . n == 0 or with both its reflectance and transmittance zero; so
-        // is a smooth one, a smooth conductor is one-sided)
+        // is a smooth one, a smooth conductor is one-sided; the twosided
+        // adapter makes its BSDF live from behind too: back)
         const float cos_i = dot3(wi, n);
+        back = twosided_back(S, qb, cos_i);
         const bool side = DIEL && (kind == kBsdfDielectric || kind == kBsdfSmoothDielectric)
                               ? (cos_i > 0.0f || cos_i < 0.0f)
-                              : cos_i > 0.0f;
+                              : (cos_i > 0.0f || back);
         if (!side || (zero_diff && zero_spec)) live = false;
         if (DIEL) pure_delta = kind == kBsdfSmoothDielectric || kind == kBsdfSmoothConductor;
     }
@@ -314,6 +322,10 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     Q.c2[i] = (p[2] - S.smin[2]) / S.snorm;
     float s[3], t[3], w[3];
     frame_of(n, s, t);
+    // a back hit: the frame (s, t, -n) -- Frame(n)'s tangents kept, so local
+    // wi is (wi.s, wi.t, -(wi.n)) and w goes to world as s w0 + t w1 - n w2
+    if (back)
+        for (int a = 0; a < 3; ++a) n[a] = -n[a];
     const float* bp = S.bpar ? S.bpar + kBsdfParams * prim_bsdf<MESH>(S, q) : nullptr;
     uint8_t delta = 0;
     if (bp && bp[0] == (float)kBsdfPlastic) {
@@ -418,10 +430,20 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
     Q.k_mode[j] = Q.mode[i];
     Q.slot[i] = j;
     if (product) {
-        const float* qn = prim_n<MESH>(S, P.quad[i]);
+        const float* pn = prim_n<MESH>(S, P.quad[i]);
         const int qb = prim_bsdf<MESH>(S, P.quad[i]);
         float s[3], t[3];
-        frame_of(qn, s, t);
+        frame_of(pn, s, t);
+        // a back hit on a two-sided BSDF: F = [s t -n] and the learned model
+        // conditioned on the flipped local wi -- getDMM's negated column 2 of
+        // `to` and mean.z (twosided.cpp:151-159) under [s t n]
+        // (sdmm_proc.cpp:344-354) are the unflipped lobes under [s t -n]
+        float qn[3] = {pn[0], pn[1], pn[2]};
+        if (S.twosided) {
+            const float wi[3] = {-P.dx[i], -P.dy[i], -P.dz[i]};
+            if (twosided_back(S, qb, dot3(wi, qn)))
+                for (int a = 0; a < 3; ++a) qn[a] = -qn[a];
+        }
         for (int r = 0; r < 3; ++r) {
             Q.k_F[3 * r][j] = s[r];
             Q.k_F[3 * r + 1][j] = t[r];
@@ -512,9 +534,15 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     LI_MESH_STACK(stack)
     const int pq = P.quad[i];
     const float* qn = prim_n<MESH>(S, pq);
-    const float n[3] = {qn[0], qn[1], qn[2]};
+    float n[3] = {qn[0], qn[1], qn[2]};
+    // a two-sided BSDF met from behind: n is the effective normal -n from here
+    // on (cosines, the saved vertex); the tangents stay Frame(qn)'s
+    if (S.twosided) {
+        const float wi[3] = {-P.dx[i], -P.dy[i], -P.dz[i]};
+        if (twosided_back(S, prim_bsdf<MESH>(S, pq), dot3(wi, n)))
+            for (int a = 0; a < 3; ++a) n[a] = -n[a];
+    }
     const float* rho = S.refl + 3 * prim_bsdf<MESH>(S, pq);
-    const float c[3] = {Q.c0[i], Q.c1[i], Q.c2[i]};
     const int j = Q.slot[i];            // the path's guided query (-1: none, BSDF only)
     const int comp = j >= 0 ? Q.comp[j] : -1;
     const bool valid = comp != -1;      // validConditional (:368)
@@ -585,7 +613,7 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         } else {
             wo[0] = Q.d0[j]; wo[1] = Q.d1[j]; wo[2] = Q.d2[j];
             float s[3], t[3];
-            frame_of(n, s, t);
+            frame_of(qn, s, t);
             const float wi[3] = {-P.dx[i], -P.dy[i], -P.dz[i]};
             const float wil[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};
             const float wol[3] = {dot3(wo, s), dot3(wo, t), dot3(wo, n)};
@@ -619,7 +647,7 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         } else {
             wo[0] = Q.d0[j]; wo[1] = Q.d1[j]; wo[2] = Q.d2[j];
             float s[3], t[3];
-            frame_of(n, s, t);
+            frame_of(qn, s, t);
             const float wil[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};
             const float wol[3] = {dot3(wo, s), dot3(wo, t), dot3(wo, n)};
             const bool zero = (wo[0] == 0.0f && wo[1] == 0.0f && wo[2] == 0.0f) || !__builtin_isfinite(wol[2]);
@@ -690,6 +718,9 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     P.nray[i] += 1;
     // the saved vertex (cacheable: not a delta lobe, :764, :821-845)
     if (cacheable && nv < P.V) {
+        // (the condition is read here, not at the top: it is needed nowhere
+        // else, and its three registers stay free over the bounce and the trace)
+        const float c[3] = {Q.c0[i], Q.c1[i], Q.c2[i]};
         const float clamped = fmaxf(mis_pdf, 0.1f);
         const float inv_pdf = 1.0f / clamped;
         for (int ch = 0; ch < 3; ++ch) {
@@ -700,7 +731,8 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         for (int a = 0; a < 3; ++a) {
             vrec(P, 7 + a, nv, i) = c[a];
             vrec(P, 10 + a, nv, i) = wo[a];
-            // (inside a dielectric the vertex carries the inward normal, :765-767)
+            // (inside a dielectric the vertex carries the inward normal,
+            // :765-767; behind a two-sided BSDF n already is the flipped one)
             vrec(P, 13 + a, nv, i) = DIEL && inside ? -n[a] : n[a];
         }
         P.nv[i] = nv + 1;

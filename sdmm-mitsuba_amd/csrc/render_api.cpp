@@ -37,6 +37,7 @@ struct sdmm_scene {
     float* dbpar = nullptr;
     float* dlmod = nullptr;   // kLearnedStride per BSDF (learned_models), null: none
     float* dlmod_nd = nullptr;   // kLearnedNdStride per BSDF (learned_models_nd), null: none
+    int32_t* dtwosided = nullptr;   // 1 per two-sided BSDF (bsdf_twosided), null: no entry set
     float* drad = nullptr;
     BvhNode* dnodes = nullptr;   // the triangle mesh (mesh_bvh.h), null without one
     MeshTri* dtris = nullptr;
@@ -235,11 +236,31 @@ int prep_env(const sdmm_scene_desc* d, const char* who, EnvDev* E) {
     return SDMM_OK;
 }
 
+// the description's two-sided flags, validated (after geometry_args_ok); *any
+// (nullable): some entry is set.  0, or the error code (message set).
+int prep_twosided(const sdmm_scene_desc* d, const char* who, bool* any) {
+    const std::string w(who);
+    if (any) *any = false;
+    if (!d->bsdf_twosided) return SDMM_OK;
+    for (int b = 0; b < d->n_bsdfs; ++b) {
+        const int32_t v = d->bsdf_twosided[b];
+        if (v != 0 && v != 1) return fail(SDMM_E_INVALID, w + ": a bsdf_twosided entry other than 0 or 1");
+        if (v == 0) continue;
+        // "Only materials without a transmission component can be nested" (twosided.cpp:106-108)
+        const float kind = d->bsdf_params ? d->bsdf_params[kBsdfParams * b] : (float)kBsdfDiffuse;
+        if (kind == (float)kBsdfDielectric || kind == (float)kBsdfSmoothDielectric)
+            return fail(SDMM_E_INVALID, w + ": bsdf_twosided on a transmitting BSDF (kind 4 or 5)");
+        if (any) *any = true;
+    }
+    return SDMM_OK;
+}
+
 // the quads' derived data (normal, duals) and their corners' AABB, after the
 // description's argument checks.  0, or the error code (message set).
 int prep_quads(const sdmm_scene_desc* d, const char* who, std::vector<QuadDev>* qs, float mn[3], float mx[3]) {
     const std::string w(who);
     if (!geometry_args_ok(d)) return fail(SDMM_E_INVALID, w + ": invalid description");
+    if (const int rc = prep_twosided(d, who, nullptr)) return rc;
     if (has_emitters(d) && (d->n_emitters < 1 || !d->radiance))
         return fail(SDMM_E_INVALID, w + ": emitters without radiance");
     qs->assign((size_t)d->n_quads, QuadDev{});
@@ -401,6 +422,9 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     int rc = prep_quads(d, "sdmm_scene_create", &qs, mn, mx);
     if (rc) return rc;
+    bool twosided = false;   // (validated in prep_quads; all zeros: no device table)
+    rc = prep_twosided(d, "sdmm_scene_create", &twosided);
+    if (rc) return rc;
     // the triangle mesh: validated, its BVH built; the AABB takes its vertices in
     MeshBvh mesh;
     if (d->n_triangles > 0) {
@@ -474,6 +498,9 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     if (e == hipSuccess && !lmod_nd.empty()) e = hipMalloc(&s->dlmod_nd, sizeof(float) * lmod_nd.size());
     if (e == hipSuccess && !lmod_nd.empty())
         e = hipMemcpy(s->dlmod_nd, lmod_nd.data(), sizeof(float) * lmod_nd.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && twosided) e = hipMalloc(&s->dtwosided, sizeof(int32_t) * (size_t)d->n_bsdfs);
+    if (e == hipSuccess && twosided)
+        e = hipMemcpy(s->dtwosided, d->bsdf_twosided, sizeof(int32_t) * (size_t)d->n_bsdfs, hipMemcpyHostToDevice);
     if (e == hipSuccess && !qs.empty())
         e = hipMemcpy(s->dquads, qs.data(), sizeof(QuadDev) * qs.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess)
@@ -491,6 +518,7 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     S.bpar = s->dbpar;
     S.lmodel = s->dlmod;
     S.lmodel_nd = s->dlmod_nd;
+    S.twosided = s->dtwosided;
     S.nodes = s->dnodes;
     S.tris = s->dtris;
     S.hits = s->dhits;
@@ -732,6 +760,7 @@ void sdmm_scene_destroy(sdmm_scene* s) {
     if (s->dbpar) (void)hipFree(s->dbpar);
     if (s->dlmod) (void)hipFree(s->dlmod);
     if (s->dlmod_nd) (void)hipFree(s->dlmod_nd);
+    if (s->dtwosided) (void)hipFree(s->dtwosided);
     if (s->drad) (void)hipFree(s->drad);
     if (s->dnodes) (void)hipFree(s->dnodes);
     if (s->dtris) (void)hipFree(s->dtris);

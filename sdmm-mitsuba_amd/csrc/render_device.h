@@ -88,7 +88,17 @@ struct SceneDev {
     // environment emitter (envmap.h): kind 0 without one; otherwise the camera
     // and shade kernels' ENV variants run
     EnvDev env;
+    // 1 per BSDF wrapped in the single-child twosided adapter (twosided.cpp);
+    // null: no BSDF is, and every kernel takes today's one-sided rule
+    const int32_t* twosided;
 };
+
+// a hit from behind (cos_i = wi . n < 0) on a two-sided BSDF: the bounce runs
+// in (s, t, -n) of Frame(n) (wi.z *= -1 ... wo.z *= -1, twosided.cpp:111-137,
+// :191-213) and the saved vertex carries -n (sdmm_proc.cpp:765-767)
+__device__ __forceinline__ bool twosided_back(const SceneDev& S, int bsdf, float cos_i) {
+    return S.twosided && S.twosided[bsdf] != 0 && cos_i < 0.0f;
+}
 
 // closest quad with t in (mint, maxt), the lowest id on equal t (strict <);
 // -1: none, *t_hit = maxt then.  Host + device, bitwise alike.

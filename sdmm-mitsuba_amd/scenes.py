@@ -259,7 +259,7 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
                 phong_learned=LEARNED_PHONG, phong_specular=(0.4, 0.4, 0.4), phong_exponent=30.0, dielectric=(),
                 dielectric_learned=LEARNED_DIELECTRIC, dielectric_alpha=0.1, dielectric_ior=(1.5046, 1.000277),
                 dielectric_specular=(1.0, 1.0, 1.0), dielectric_transmittance=(1.0, 1.0, 1.0), dielectric_lift=0.0,
-                mesh=(), glass=(), mirror=(), mirror_eta_k=(1.2, 7.0)):
+                mesh=(), glass=(), mirror=(), mirror_eta_k=(1.2, 7.0), twosided=()):
     """sdmm_scene_desc fields for the Cornell Box (numpy arrays).  plastic:
     names of BSDFs (e.g. "TallBox", "ShortBox", "Floor") rendered as smooth
     plastic over their diffuse reflectance (a delta specular lobe beside a
@@ -287,7 +287,10 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
     / _ior, a glass cube lifted by dielectric_lift like a rough one; mirror:
     names rendered as smooth conductors (kind 6) tinted by their reflectance
     like `conductor`, with the gray mirror_eta_k = (eta, k).  Neither reads a
-    learned model: their bounces are delta only."""
+    learned model: their bounces are delta only.
+    twosided: names wrapped in the single-child `twosided` adapter (the
+    description's bsdf_twosided; not a `dielectric` or `glass` name, which
+    transmit).  The box is closed, so no path meets such a BSDF from behind."""
     names = list(_BSDFS)
     quads, bsdf, flip, emitter = [], [], [], []
     mesh_quads, mesh_bsdf = [], []
@@ -348,6 +351,11 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
             model = load_learned_nd(dielectric_learned)
             nd = extra.setdefault("learned_models_nd", [None] * len(names))
             extra["learned_models_nd"] = [model if nm in dielectric else cur for nm, cur in zip(names, nd)]
+    if twosided:
+        bad = (set(twosided) - set(names)) | (set(twosided) & (set(dielectric) | set(glass)))
+        if bad:
+            raise ValueError(f"twosided: unknown or transmitting BSDFs {sorted(bad)}")
+        extra["bsdf_twosided"] = np.asarray([int(nm in twosided) for nm in names], np.int32)
     return {**extra,
         "quads": np.asarray(quads, np.float32).reshape(-1),
         "flip_normals": np.asarray(flip, np.int32),
@@ -558,6 +566,147 @@ def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=Non
         "width": width,
         "height": height,
     }
+
+
+def sheet_mesh(nx, nz, x=(-1.8, 1.8), z=(1.4, -2.6), y0=1.6, amplitude=0.45, waves=1.25, phase=np.pi):
+    """An open sheet: the height field y = y0 + amplitude sin(2 pi waves s +
+    phase) over x[0]..x[1] and, along s in [0, 1], z[0]..z[1], as nx x nz
+    cells of two triangles with the face normals on the +y side: (vertices
+    [(nx + 1)(nz + 1), 3] float32, triangles [2 nx nz, 3] int32)."""
+    a = np.linspace(0.0, 1.0, nx + 1)
+    s = np.linspace(0.0, 1.0, nz + 1)
+    aa, ss = np.meshgrid(a, s, indexing="ij")
+    P = np.stack([x[0] + (x[1] - x[0]) * aa, y0 + amplitude * np.sin(2.0 * np.pi * waves * ss + phase),
+                  z[0] + (z[1] - z[0]) * ss], -1).reshape(-1, 3)
+    i, j = np.meshgrid(np.arange(nx), np.arange(nz), indexing="ij")
+    p00 = (i * (nz + 1) + j).reshape(-1)
+    p10, p01, p11 = p00 + (nz + 1), p00 + 1, p00 + (nz + 1) + 1
+    tris = np.concatenate([np.stack([p00, p10, p11], -1), np.stack([p00, p11, p01], -1)], 1).reshape(-1, 3)
+    # (dP/da) x (dP/ds) points along +y when x grows with a and z falls with s
+    if (x[1] - x[0]) * (z[1] - z[0]) > 0:
+        tris = tris[:, ::-1]
+    return P.astype(np.float32), np.ascontiguousarray(tris, np.int32)
+
+
+SHEET_MATERIALS = ("diffuse", "plastic", "conductor", "phong", "mirror")   # kinds 0, 1, 2, 3, 6
+
+
+def sheet_scene(width=640, height=360, nx=16, nz=48, material="diffuse", twosided=True, environment=None,
+                reflectance=(0.7, 0.6, 0.4), learned=True, patch=False):
+    """An open surface for the `twosided` adapter: torus_scene's lit room (or,
+    with environment=, its open floor under that sky) holding a sheet --
+    sheet_mesh(nx, nz), a sine wave hanging at the camera's height and running
+    away from it, so the camera looks under its near edge at the back of the
+    first slope and over that edge at the front of the slopes behind it.
+    Every face normal is on the sheet's upper side: the lamp lights the front,
+    the floor's bounce the back.  material: one of SHEET_MATERIALS (kinds 0,
+    1, 2, 3 and 6) over `reflectance`, parametrised as cornell_box's plastic /
+    conductor / phong / mirror; learned: a conductor or Phong sheet carries
+    the shipped learned model.  twosided: the sheet's BSDF is under the
+    adapter (the default; False: the one-sided BSDF, black from behind).
+    patch: a two-sided rough-conductor quad (alpha 0.2, its learned SDMM4)
+    lying face up above the sheet and the camera: what reaches it from below
+    meets its back, and in the open scene (environment=) nothing lies above
+    it, so every hit on it is one from behind."""
+    if material not in SHEET_MATERIALS:
+        raise ValueError(f"material: one of {SHEET_MATERIALS}")
+    names = ["Room", "Floor", "Sheet", "Light"] + (["Patch"] if patch else [])
+    refl = {"Room": (0.6, 0.6, 0.6), "Floor": (0.5, 0.5, 0.5), "Sheet": tuple(reflectance), "Light": (0.0, 0.0, 0.0),
+            "Patch": (0.0, 0.0, 0.0)}
+    quads, bsdf, emitter = [], [], []
+    if environment is None:
+        M = np.zeros((3, 4))
+        M[:, :3] = np.diag([4.0, 2.5, 4.0])
+        M[:, 3] = (0.0, 2.5, 0.0)
+        for k, (p0, e1, e2) in enumerate(_cube_faces(M)):
+            if k == 3:                          # the face y = 0: the floor below
+                continue
+            quads.append(np.concatenate((p0, e2, e1)))     # inward
+            bsdf.append(names.index("Room")); emitter.append(-1)
+    quads.append(np.array([-4.0, 0.0, -4.0, 0.0, 0.0, 8.0, 8.0, 0.0, 0.0]))      # floor, normal +y
+    bsdf.append(names.index("Floor")); emitter.append(-1)
+    if environment is None:
+        quads.append(np.array([-1.5, 4.99, -1.5, 3.0, 0.0, 0.0, 0.0, 0.0, 3.0]))     # lamp, normal -y
+        bsdf.append(names.index("Light")); emitter.append(0)
+    if patch:
+        quads.append(np.array([-3.6, 3.2, -3.6, 0.0, 0.0, 2.4, 2.4, 0.0, 0.0]))     # normal +y: seen from below
+        bsdf.append(names.index("Patch")); emitter.append(-1)
+    bp = np.zeros((len(names), 8), np.float32)
+    b = names.index("Sheet")
+    extra = {}
+    tint = tuple(min(1.0, 1.25 * c) for c in reflectance)
+    models = [None] * len(names)
+    if material == "plastic":
+        bp[b] = plastic_params(reflectance)
+    elif material == "conductor":
+        bp[b] = conductor_params(tint)
+        if learned:
+            models[b] = load_learned(LEARNED_CONDUCTOR)
+    elif material == "phong":
+        bp[b], refl["Sheet"] = phong_params(reflectance, (0.4, 0.4, 0.4), 30.0)
+        if learned:
+            extra["learned_models_nd"] = [load_learned_nd(LEARNED_PHONG) if nm == "Sheet" else None for nm in names]
+    elif material == "mirror":
+        bp[b] = smooth_conductor_params(tint)
+    if patch:
+        bp[names.index("Patch")] = conductor_params((0.9, 0.9, 0.9))
+        models[names.index("Patch")] = load_learned(LEARNED_CONDUCTOR)
+    if any(m is not None for m in models):
+        extra["learned_models"] = models
+    if twosided:
+        extra["bsdf_twosided"] = np.asarray([int(nm in ("Sheet", "Patch")) for nm in names], np.int32)
+    if environment is not None:
+        extra.update(environment)
+    verts, tris = sheet_mesh(nx, nz)
+    return {**extra,
+        "quads": np.asarray(quads, np.float32).reshape(-1),
+        "bsdf": np.asarray(bsdf, np.int32),
+        "bsdf_params": bp.reshape(-1),
+        "reflectance": np.asarray([refl[n] for n in names], np.float32).reshape(-1),
+        "emitter": np.asarray(emitter, np.int32),
+        "radiance": np.asarray([12.0, 12.0, 12.0], np.float32),
+        "mesh_vertices": verts.reshape(-1),
+        "triangles": tris.reshape(-1),
+        "tri_bsdf": np.full(len(tris), b, np.int32),
+        "camera_to_world": _look_at((0.0, 1.75, 3.9), (0.0, 1.5, 0.0), (0.0, 1.0, 0.0)),
+        "fov_x_deg": 45.0,
+        "near_clip": 1e-2,
+        "width": width,
+        "height": height,
+    }
+
+
+def mirror_z(desc, keep=()):
+    """The description's mirror image in the plane z = 0: every z coordinate
+    negated (quad corners and edges, mesh vertices, the camera's position and
+    the z row of its axes), flip_normals toggled on every quad and triangle
+    except those listed in `keep` (quad ids; a triangle is n_quads + its
+    index) -- the mirror reverses a primitive's winding, so toggling keeps its
+    normal the mirrored one, and a kept primitive keeps the normal it had: it
+    is then met from the other side.  Order and every other field are the
+    same; the environment's transform is not mirrored."""
+    out = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in desc.items()}
+    keep = set(int(k) for k in keep)
+    nq = 0
+    if "quads" in desc and np.asarray(desc["quads"]).size:
+        q = np.array(desc["quads"], np.float32).reshape(-1, 3, 3)
+        q[:, :, 2] = -q[:, :, 2]
+        nq = len(q)
+        out["quads"] = q.reshape(-1)
+        fl = np.array(desc.get("flip_normals", np.zeros(nq, np.int32)), np.int32)
+        out["flip_normals"] = np.asarray([f if i in keep else 1 - f for i, f in enumerate(fl)], np.int32)
+    if "mesh_vertices" in desc:
+        v = np.array(desc["mesh_vertices"], np.float32).reshape(-1, 3)
+        v[:, 2] = -v[:, 2]
+        out["mesh_vertices"] = v.reshape(-1)
+        nt = np.asarray(desc["triangles"]).size // 3
+        fl = np.array(desc["tri_flip_normals"], np.int32) if desc.get("tri_flip_normals") is not None \
+            else np.zeros(nt, np.int32)
+        out["tri_flip_normals"] = np.asarray([f if nq + i in keep else 1 - f for i, f in enumerate(fl)], np.int32)
+    cam = np.array(desc["camera_to_world"], np.float32).reshape(4, 4)
+    cam[2, :] = -cam[2, :]
+    out["camera_to_world"] = cam.reshape(-1)
+    return out
 
 
 def diffuse_learned_bsdf(n_bsdfs: int, sigma: float = 0.65):

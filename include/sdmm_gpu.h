@@ -863,7 +863,7 @@ typedef struct {
      *                     when it is set, also without a quad `emitter`)
      *   tri_flip_normals  nullable
      * The normal is the face normal normalize((p1 - p0) x (p2 - p0)), negated
-     * where flipped.  Vertex and shading normals, UVs, textures and
+     * where flipped (vertex normals: mesh_normals below).  UVs, textures and
      * instancing are not supported.  n_quads may be 0 with triangles.
      * Primitive ids: quads 0 .. n_quads-1, triangle i is n_quads + i; the
      * learned-BSDF row of a hit is still its bsdf index, and the scene AABB
@@ -943,10 +943,43 @@ typedef struct {
      * kind-4 or kind-5 BSDF ("Only materials without a transmission component
      * can be nested", :106-108).
      * Not supported: the two-child form (m_nestedBRDF[1] != [0]; there getDMM
-     * always asks child 0, :146), vertex and shading normals, textures,
-     * two-sided emitters; the Mitsuba plugin does not run the device Li, so
+     * always asks child 0, :146), textures, two-sided emitters (with
+     * mesh_normals the stored normal n above is the hit's shading normal ns); the Mitsuba plugin does not run the device Li, so
      * it takes no such flag. */
     const int32_t* bsdf_twosided;
+    /* nullable: vertex normals of the mesh, 3 floats per mesh vertex in world
+     * space (appended after bsdf_twosided; the zero-initialise rule below
+     * covers older callers: NULL and every rule above holds, bit for bit).
+     * The values are used as given: vertex normals are not normalised, the
+     * interpolated sum is (render/skdtree.h:388).  At a hit on triangle (i0,
+     * i1, i2) with the triangle test's own u, v:
+     *   b  = (1 - u - v, u, v)
+     *   ns = normalize(n[i0] b.x + n[i1] b.y + n[i2] b.z), negated where
+     *        tri_flip_normals is set (Mitsuba's per-mesh flipNormals negates
+     *        the vertex normals, trimesh.cpp:624-628; the winding is left
+     *        alone when normals are present)
+     *   ng = the winding's face normal normalize((p1 - p0) x (p2 - p0)),
+     *        without the flip, negated when dot(ng, ns) < 0 (skdtree.h:390-396)
+     * Everything the Li did on the face normal it does on ns: the side tests
+     * (cos_i, the two-sided back hit, inside a dielectric), Frame(ns) for
+     * every toLocal / toWorld, the cosine pdfs, the product's F = [s t +-ns]
+     * and the learned conditionals' local wi, the guide's condition normal
+     * and the saved vertex's normal (fields 13-15; -ns behind a two-sided BSDF
+     * or inside a dielectric), and an emitting triangle is seen where
+     * dot(ns, d) < 0 (emitters/area.cpp:105).  ng appears only in the
+     * strictNormals tests (sdmm_li_params.non_strict_normals).  Quads, and a
+     * mesh without mesh_normals, keep ns = ng = the face normal.
+     * Documented choices: the shading frame stays Frame(ns) (coordinateSystem)
+     * and is not Mitsuba's computeShadingFrame(ns, dpdu) -- all seven BSDF
+     * kinds are isotropic, so the tangents only move bits; the sum is divided
+     * by its length where Mitsuba multiplies by the reciprocal, so exact
+     * axis-aligned vertex normals reproduce the face normal bit for bit; and
+     * where the interpolated sum has length 0 or is not finite, ns = ng = the
+     * face normal (flip applied) as without normals -- Mitsuba would carry a
+     * NaN there.
+     * SDMM_E_INVALID (with a message): mesh_normals set without triangles; a
+     * non-finite normal; a normal of length 0 (all three components 0). */
+    const float* mesh_normals;
 } sdmm_scene_desc;
 /* The descriptor has grown across ABI revisions (bsdf_params was appended):
  * zero-initialise it (`sdmm_scene_desc d = {0};` / `memset`) before filling
@@ -984,6 +1017,19 @@ typedef struct {
      * unreachable in the reference.) */
     int sample_product;
     sdmm_bsdf_table learned_bsdf;   /* device arrays */
+    /* strictNormals (volpath_sdmm.cpp:54; appended: a zero-initialised struct
+     * is the reference's default, strictNormals = true, and today's
+     * behaviour).  0: a bounce ends where the incident direction lies on
+     * different sides of the two normals, (wi . ng)(wi . ns) < 0, tested after
+     * the depth test and before any BSDF sample (sdmm_proc.cpp:688-691), and
+     * where the sampled direction does, (wo . ng) cosTheta(bRec.wo) <= 0
+     * (:777-780; bRec.wo is in its.shFrame also behind a two-sided BSDF,
+     * twosided.cpp:137, so the product is (wo . ng)(wo . ns)).  Not 0:
+     * neither test runs; a zero or non-finite weight still ends the path.
+     * Without sdmm_scene_desc.mesh_normals ns = ng, the first test never
+     * fires, the second is cos^2 > 0 as it always was, and the field is not
+     * read. */
+    int non_strict_normals;
 } sdmm_li_params;
 /* Vertex records of the last render (device): field f of vertex v of path p
  * at rec[(f * max_vertices + v) * n_paths + p]; f: 0-2 weight (RGB), 3-5
@@ -1038,6 +1084,20 @@ int sdmm_scene_intersect_host(const sdmm_scene_desc* desc, int64_t nq, const flo
  * sdmm_mesh_bvh_dump).  The hits do not depend on the cap. */
 int sdmm_scene_intersect_host_levels(const sdmm_scene_desc* desc, int max_levels, int64_t nq, const float* o,
                                      const float* d, float mint, float maxt, int mode, int32_t* prim, float* t);
+/* sdmm_scene_intersect extended by the hit's two normals as the Li kernels
+ * compute them (sdmm_scene_desc.mesh_normals): ns, ng three device planes
+ * each, the shading and the geometric normal, zeros on a miss; on a quad, or
+ * on a triangle of a mesh without vertex normals, both are the face normal
+ * (flip applied).  Asynchronous on hip_stream. */
+int sdmm_scene_shading(const sdmm_scene* s, int64_t nq, const float* const o[3], const float* const d[3], float mint,
+                       float maxt, int mode, int32_t* prim, float* t, float* const ns[3], float* const ng[3],
+                       void* hip_stream);
+/* The same entirely on the host (no HIP call: runs without a GPU) from a
+ * description -- o, d host arrays [nq][3], ns, ng host arrays [nq][3].
+ * Validates as sdmm_scene_create does; one source (csrc/shading_normal.h)
+ * serves this entry, the device entry and the Li kernels, bitwise alike. */
+int sdmm_scene_shading_host(const sdmm_scene_desc* desc, int64_t nq, const float* o, const float* d, float mint,
+                            float maxt, int mode, int32_t* prim, float* t, float* ns, float* ng);
 /* evalEnvironment of the scene's environment emitter (sdmm_scene_desc's env
  * fields) for nq directions: d, rgb three device planes each (the direction
  * is used as given; rgb: the radiance, 0 for a scene without an environment).

@@ -177,6 +177,10 @@ def lib():
                                                 C.c_int, C.c_void_p, C.c_void_p]
         L.sdmm_scene_intersect_host_levels.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                                        C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        L.sdmm_scene_shading.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sdmm_scene_shading_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdmm_env_eval.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdmm_env_eval_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.sdmm_mesh_bvh_dump.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
@@ -300,7 +304,7 @@ EXPORTED_SYMBOLS = [
     "sdmm_bsdf_roughdielectric_host", "sdmm_bsdf_roughdielectric_device",
     "sdmm_bsdf_smooth_host", "sdmm_bsdf_smooth_device",
     "sdmm_scene_intersect", "sdmm_scene_intersect_host", "sdmm_scene_intersect_host_levels",
-    "sdmm_mesh_bvh_dump",
+    "sdmm_mesh_bvh_dump", "sdmm_scene_shading", "sdmm_scene_shading_host",
     "sdmm_env_eval", "sdmm_env_eval_host",
     "sdmm_read_exr", "sdmm_film_create", "sdmm_film_destroy", "sdmm_film_add_pass", "sdmm_film_passes",
     "sdmm_film_pass_stats", "sdmm_film_resolve", "sdmm_film_errors", "sdmm_film_variance", "sdmm_film_reset",
@@ -1478,7 +1482,8 @@ class _SceneDesc(C.Structure):
                 ("tri_flip_normals", C.c_void_p),
                 ("env_kind", C.c_int), ("env_radiance", C.c_float * 3), ("env_width", C.c_int),
                 ("env_height", C.c_int), ("env_pixels", C.c_void_p), ("env_scale", C.c_float),
-                ("env_world_to_local", C.c_float * 9), ("bsdf_twosided", C.c_void_p)]
+                ("env_world_to_local", C.c_float * 9), ("bsdf_twosided", C.c_void_p),
+                ("mesh_normals", C.c_void_p)]
 
 
 def _fill_geometry(d, desc, keep):
@@ -1510,6 +1515,11 @@ def _fill_geometry(d, desc, keep):
     for key in ("tri_bsdf", "tri_emitter", "tri_flip_normals"):
         if desc.get(key) is not None:
             setattr(d, key, arr(key, np.int32).ctypes.data)
+    # vertex normals: 3 floats per mesh vertex, world space, used as given
+    if desc.get("mesh_normals") is not None:
+        if np.asarray(desc["mesh_normals"]).size != 3 * d.n_mesh_vertices:
+            raise SDMMError("mesh_normals: 3 floats per mesh vertex")
+        d.mesh_normals = arr("mesh_normals", np.float32).ctypes.data
     # per BSDF: 1 = under the twosided adapter (and the kind, which the flag's validation reads)
     if desc.get("bsdf_twosided") is not None:
         if np.asarray(desc["bsdf_twosided"]).size != d.n_bsdfs:
@@ -1574,6 +1584,27 @@ def intersect_host(desc, o, d, mint=1e-4, maxt=float("inf"), mode=0, max_levels=
                                                   float(mint), float(maxt), int(mode), prim.ctypes.data,
                                                   t.ctypes.data))
     return prim, t
+
+
+def shading_host(desc, o, d, mint=1e-4, maxt=float("inf"), mode=0):
+    """sdmm_scene_shading_host: intersect_host plus the hit's shading and
+    geometric normal as the Li kernels compute them (desc["mesh_normals"]:
+    vertex normals), entirely on the host (no GPU).  (prim int32[nq], t
+    float32[nq], ns float32[nq, 3], ng float32[nq, 3]); zeros on a miss, the
+    face normal twice on a quad or on a mesh without vertex normals."""
+    sd, keep = _SceneDesc(), {}
+    _fill_geometry(sd, desc, keep)
+    o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+    dd = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    if o.shape != dd.shape:
+        raise SDMMError("o and d: [nq, 3] each")
+    prim = np.empty(len(o), np.int32)
+    t = np.empty(len(o), np.float32)
+    ns = np.empty((len(o), 3), np.float32)
+    ng = np.empty((len(o), 3), np.float32)
+    _check(lib().sdmm_scene_shading_host(C.byref(sd), len(o), o.ctypes.data, dd.ctypes.data, float(mint), float(maxt),
+                                         int(mode), prim.ctypes.data, t.ctypes.data, ns.ctypes.data, ng.ctypes.data))
+    return prim, t, ns, ng
 
 
 def mesh_bvh_dump(desc, max_levels=0):
@@ -1875,7 +1906,7 @@ class _LiParams(C.Structure):
     _fields_ = [("spp", C.c_int), ("max_depth", C.c_int), ("rr_depth", C.c_int), ("guided", C.c_int),
                 ("bsdf_fraction", C.c_float), ("saved_vertices", C.c_int), ("seed", C.c_uint64),
                 ("pixel_begin", C.c_int64), ("pixel_end", C.c_int64), ("sample_product", C.c_int),
-                ("learned_bsdf", _BsdfTable)]
+                ("learned_bsdf", _BsdfTable), ("non_strict_normals", C.c_int)]
 
 
 class _PathVertices(C.Structure):
@@ -2075,6 +2106,31 @@ class Scene:
                                           C.c_void_p(int(s_.cuda_stream) or None)))
         return prim, t
 
+    def shading(self, o, d, mint=1e-4, maxt=float("inf"), mode=0, stream=None):
+        """sdmm_scene_shading: intersect plus the hit's shading and geometric
+        normal as the Li kernels compute them -- o, d: 3 float32 device
+        tensors of nq each.  (prim int32[nq], t float32[nq], ns, ng: 3 float32
+        device tensors each; zeros on a miss); bitwise shading_host's."""
+        import torch
+        nq = o[0].numel()
+        dev = o[0].device
+        for t_ in list(o) + list(d):
+            if t_.numel() != nq or t_.dtype != torch.float32 or not t_.is_contiguous() or t_.device != dev:
+                raise SDMMError("planes: contiguous float32 device tensors of one value per ray")
+        prim = torch.empty(nq, device=dev, dtype=torch.int32)
+        t = torch.empty(nq, device=dev)
+        ns = [torch.empty(nq, device=dev) for _ in range(3)]
+        ng = [torch.empty(nq, device=dev) for _ in range(3)]
+        s_ = torch.cuda.current_stream(dev) if stream is None else stream
+        P3 = C.c_void_p * 3
+        _check(lib().sdmm_scene_shading(self.h, nq, C.cast(P3(*[x.data_ptr() for x in o]), C.c_void_p),
+                                        C.cast(P3(*[x.data_ptr() for x in d]), C.c_void_p), float(mint), float(maxt),
+                                        int(mode), prim.data_ptr(), t.data_ptr(),
+                                        C.cast(P3(*[x.data_ptr() for x in ns]), C.c_void_p),
+                                        C.cast(P3(*[x.data_ptr() for x in ng]), C.c_void_p),
+                                        C.c_void_p(int(s_.cuda_stream) or None)))
+        return prim, t, ns, ng
+
     def env_eval(self, d, stream=None):
         """sdmm_env_eval: the environment emitter's radiance for directions on
         device planes -- d: 3 float32 device tensors of nq each -> 3 float32
@@ -2095,10 +2151,14 @@ class Scene:
 
     def render(self, tree: "STree", node_mix=None, spp: int = 1, max_depth: int = 10, rr_depth: int = 10,
                guided: bool = False, bsdf_fraction: float = 0.5, saved_vertices: int = 9, seed: int = 0,
-               pixels=None, image=None, image_sqr=None, learned_bsdf: "BsdfTable" = None):
+               pixels=None, image=None, image_sqr=None, learned_bsdf: "BsdfTable" = None,
+               strict_normals: bool = True):
         """One render pass (sdmm_li_render) -> (image (3, H, W) device tensor,
         PathVertices, stats dict).  learned_bsdf: sampleProduct with that
-        learned-BSDF table (one row per scene BSDF)."""
+        learned-BSDF table (one row per scene BSDF).  strict_normals: the
+        reference's strictNormals (its default, True): with vertex normals a
+        bounce ends where wi or wo lies on different sides of the shading and
+        the geometric normal; without them the flag changes nothing."""
         import torch
         if image is None:
             image = torch.zeros(3, self.height, self.width, device=torch.device("cuda", self.device))
@@ -2108,6 +2168,7 @@ class Scene:
         p.pixel_begin, p.pixel_end = (0, self.width * self.height) if pixels is None else pixels
         if learned_bsdf is not None:
             p.sample_product, p.learned_bsdf = 1, learned_bsdf.c
+        p.non_strict_normals = 0 if strict_normals else 1
         v = _PathVertices()
         st = _LiStats()
         tab = None if not guided else tree._node_table(node_mix)

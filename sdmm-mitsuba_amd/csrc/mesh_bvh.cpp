@@ -187,11 +187,19 @@ bool mesh_build(const MeshInput& in, int max_levels, MeshBvh* out, std::string* 
             out->mn[a] = std::min(out->mn[a], x);
             out->mx[a] = std::max(out->mx[a], x);
         }
+    if (in.normals)
+        for (int64_t i = 0; i < (int64_t)in.n_vertices; ++i) {
+            const float* n = in.normals + 3 * i;
+            if (!std::isfinite(n[0]) || !std::isfinite(n[1]) || !std::isfinite(n[2]))
+                return fail("mesh: non-finite vertex normal");
+            if (n[0] == 0.0f && n[1] == 0.0f && n[2] == 0.0f) return fail("mesh: vertex normal of length 0");
+        }
     const int nt = in.n_triangles;
     Builder B;
     B.cap = cap;
     B.prims.resize((size_t)nt);
     out->hits.resize((size_t)nt);
+    out->shade.resize(in.normals ? (size_t)nt : 0);
     std::vector<MeshTri> prepared((size_t)nt);
     for (int i = 0; i < nt; ++i) {
         const int32_t* ix = in.triangles + 3 * (int64_t)i;
@@ -218,6 +226,16 @@ bool mesh_build(const MeshInput& in, int max_levels, MeshBvh* out, std::string* 
         H.emitter = in.emitter ? in.emitter[i] : -1;
         if (H.bsdf < 0 || H.bsdf >= in.n_bsdfs || H.emitter < -1 || (H.emitter >= 0 && H.emitter >= in.n_emitters))
             return fail("mesh: material index out of range");
+        if (in.normals) {
+            MeshShade& V = out->shade[(size_t)i];
+            V.tri = T;
+            for (int a = 0; a < 3; ++a) {
+                V.n0[a] = in.normals[3 * (int64_t)ix[0] + a];
+                V.n1[a] = in.normals[3 * (int64_t)ix[1] + a];
+                V.n2[a] = in.normals[3 * (int64_t)ix[2] + a];
+            }
+            V.flip = (in.flip && in.flip[i]) ? 1 : 0;
+        }
         Prim& P = B.prims[(size_t)i];
         P.box.add(p0);
         P.box.add(p1);

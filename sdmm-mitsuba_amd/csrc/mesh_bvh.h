@@ -17,6 +17,7 @@
 // (a runtime-indexed private array would go to scratch), the host in an array.
 #pragma once
 #include "mesh_intersect.h"
+#include "shading_normal.h"
 
 #if defined(__clang__)
 #pragma clang fp contract(off)
@@ -148,12 +149,14 @@ struct MeshInput {
     const int32_t* bsdf = nullptr;          // per triangle
     const int32_t* emitter = nullptr;       // nullable, -1: none
     const int32_t* flip = nullptr;          // nullable
+    const float* normals = nullptr;         // nullable: 3 per vertex, world, used as given
     int n_bsdfs = 0, n_emitters = 0;
 };
 
 struct MeshBvh {
     std::vector<MeshTri> tris;      // leaf order
     std::vector<MeshHit> hits;      // caller's order
+    std::vector<MeshShade> shade;   // caller's order; empty without vertex normals
     std::vector<BvhNode> nodes;     // nodes[0]: the root
     int levels = 0;                 // inner levels (root = 1)
     float mn[3], mx[3];             // AABB of all the vertices

@@ -36,8 +36,10 @@ struct MeshHit {
 };
 static_assert(sizeof(MeshHit) == 20, "MeshHit layout");
 
-// true: the ray o + t d meets the triangle at *t (any sign)
-SDMM_MESH_HD bool tri_intersect(const MeshTri& T, const float o[3], const float d[3], float* t) {
+// true: the ray o + t d meets the triangle at *t (any sign); *u, *v: the
+// test's own barycentrics of the hit, p = (1 - u - v) p0 + u p1 + v p2
+SDMM_MESH_HD bool tri_intersect_uv(const MeshTri& T, const float o[3], const float d[3], float* t, float* u_out,
+                                   float* v_out) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -55,9 +57,17 @@ SDMM_MESH_HD bool tri_intersect(const MeshTri& T, const float o[3], const float 
     // (inverted comparison: catches NaNs)
     if (v >= 0.0f && u + v <= 1.0f) {
         *t = (T.e2[0] * qvec[0] + T.e2[1] * qvec[1] + T.e2[2] * qvec[2]) * inv_det;
+        *u_out = u;
+        *v_out = v;
         return true;
     }
     return false;
+}
+// (the closest-hit search does not keep the barycentrics: shading_normal.h
+// runs the test again on the winner alone)
+SDMM_MESH_HD bool tri_intersect(const MeshTri& T, const float o[3], const float d[3], float* t) {
+    float u, v;
+    return tri_intersect_uv(T, o, d, t, &u, &v);
 }
 
 // The closest-hit rule for a triangle (every path goes through here): t in

@@ -20,8 +20,10 @@
 // film kernel averages each pixel's samples in sample order (box filter).
 //
 // Scene: parallelograms (Mitsuba rectangles; a cube is six) and an optional
-// triangle mesh (face normals; its BVH walked by the MESH variants of the
-// camera and shade kernels: mesh_bvh.h), diffuse BSDFs
+// triangle mesh (its BVH walked by the MESH variants of the camera and shade
+// kernels: mesh_bvh.h; face normals, or with sdmm_scene_desc.mesh_normals the
+// interpolated shading normal beside the geometric one, shading_normal.h, and
+// the strictNormals tests: the NRM variants), diffuse BSDFs
 // (diffuse.cpp: cosine-hemisphere sampling, f = rho / pi) and smooth plastic
 // (plastic.cpp: a delta specular lobe with the dielectric Fresnel reflectance
 // over a diffuse base, the lobe chosen by Fresnel-weighted probability), rough
@@ -31,8 +33,8 @@
 // guide and saves no vertex), each non-transmitting kind optionally under the
 // single-child twosided adapter (twosided.cpp, SceneDev::twosided: a hit from
 // behind runs the nested BSDF in (s, t, -n) of Frame(n), saves -n with its
-// vertex and hands the product F = [s t -n]; the two-child form, vertex and
-// shading normals, textures and two-sided emitters are not done),
+// vertex and hands the product F = [s t -n]; the two-child form, textures and
+// two-sided emitters are not done),
 // one-sided area emitters (area.cpp: Le = radiance on the normal side) and an
 // optional environment emitter (envmap.h: constant or lat-long map, seen by
 // every ray that leaves the scene).  No NEE (the plugin's
@@ -106,6 +108,28 @@ __device__ __forceinline__ int prim_emitter(const SceneDev& S, int q) {
     if constexpr (MESH)
         if (q >= S.n_quads) return S.hits[q - S.n_quads].emitter;
     return S.quads[q].emitter;
+}
+// NRM: the Li kernels' variants for a mesh with vertex normals (MESH only).
+// They take the normals' record as one more, last argument -- the parameter
+// pack Nrm = {NormalsDev}; the variants every other scene runs have an empty
+// pack, so their arguments are what they always were.
+__device__ __forceinline__ NormalsDev nrm_arg(NormalsDev n) { return n; }
+// The current hit's shading normal: NRM from the path's planes, where the
+// kernel that traced the ray left it -- otherwise the primitive's face normal,
+// fetched by id as ever.  buf: the caller's three floats (unused without NRM).
+template <bool MESH, class... Nrm>
+__device__ __forceinline__ const float* path_ns(const SceneDev& S, int64_t i, int q, float buf[3], Nrm... nrm) {
+    if constexpr (sizeof...(Nrm) != 0) {
+        const NormalsDev N = nrm_arg(nrm...);
+        buf[0] = N.nsx[i]; buf[1] = N.nsy[i]; buf[2] = N.nsz[i];
+        return buf;
+    } else {
+        return prim_n<MESH>(S, q);
+    }
+}
+__device__ __forceinline__ void store_normals(const NormalsDev& N, int64_t i, const float ns[3], const float ng[3]) {
+    N.nsx[i] = ns[0]; N.nsy[i] = ns[1]; N.nsz[i] = ns[2];
+    N.ngx[i] = ng[0]; N.ngy[i] = ng[1]; N.ngz[i] = ng[2];
 }
 // the MESH kernels' traversal stack: kBvhStack levels x 256 threads of LDS
 #define LI_MESH_STACK(stack)                              \
@@ -215,9 +239,15 @@ __device__ __forceinline__ void record_radiance(const PathsDev& P, int64_t p, in
 // ENV: the variant for a scene with an environment emitter (envmap.h): a ray
 // that hits nothing returns evalEnvironment (sdmm_proc.cpp:659-671); the other
 // scenes' kernels do not carry the lookup and keep their registers.
-template <bool MESH, bool ENV>
+// NRM: the variant for a mesh with vertex normals (shading_normal.h): the hit's
+// ns / ng are worked out here, once, and left in the path's planes; emission
+// is seen on the shading normal's side (dot(its.shFrame.n, d) <= 0 gives 0,
+// emitters/area.cpp:105).
+template <bool MESH, bool ENV, class... Nrm>
 __global__ void __launch_bounds__(256)
-li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) {
+li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed, Nrm... nrm) {
+    constexpr bool NRM = sizeof...(Nrm) != 0;
+    static_assert(!NRM || MESH, "NRM: a MESH variant");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.P) return;
     LI_MESH_STACK(stack)
@@ -244,7 +274,15 @@ li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) 
     P.dx[i] = d[0]; P.dy[i] = d[1]; P.dz[i] = d[2];
     float L[3] = {0.0f, 0.0f, 0.0f};
     if (q >= 0) {
-        const float* qn = prim_n<MESH>(S, q);
+        float hns[3], hng[3];
+        const float* qn;
+        if constexpr (NRM) {
+            hit_normals(S, nrm_arg(nrm...).shade, q, o, d, hns, hng);
+            store_normals(nrm_arg(nrm...), i, hns, hng);
+            qn = hns;
+        } else {
+            qn = prim_n<MESH>(S, q);
+        }
         const int qe = prim_emitter<MESH>(S, q);
         P.px[i] = o[0] + t * d[0]; P.py[i] = o[1] + t * d[1]; P.pz[i] = o[2] + t * d[2];
         // emission seen directly (:674-677), before any vertex exists
@@ -268,10 +306,15 @@ li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed) 
 // two-sided hits, the transmitted lobe and the path's relative index eta; and
 // for the delta-only BSDFs of bsdf_smooth.h (kinds 5 and 6), whose bounce takes
 // the sampled direction without a guide query (sdmm_proc.cpp:297-302).
-template <bool PHONG, bool DIEL, bool MESH>
+// NRM: with vertex normals everything here runs on the hit's shading normal,
+// and strictNormals' first test ends the path whose wi lies on different sides
+// of the two normals ((wi . ng)(wi . ns) < 0, sdmm_proc.cpp:688-691).
+template <bool PHONG, bool DIEL, bool MESH, class... Nrm>
 __global__ void __launch_bounds__(256)
 li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int max_depth, int guided,
-                float h, uint64_t seed) {
+                float h, uint64_t seed, Nrm... nrm) {
+    constexpr bool NRM = sizeof...(Nrm) != 0;
+    static_assert(!NRM || MESH, "NRM: a MESH variant");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.P) return;
     if (DIEL && bounce == 0) P.eta[i] = 1.0f;   // Float eta = 1.0f (sdmm_proc.cpp:604)
@@ -287,6 +330,15 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         const int qb = prim_bsdf<MESH>(S, q);
         n[0] = qn[0]; n[1] = qn[1]; n[2] = qn[2];
         wi[0] = -P.dx[i]; wi[1] = -P.dy[i]; wi[2] = -P.dz[i];
+        if constexpr (NRM) {
+            // (the shading normal in the face normal's place, and strictNormals' first test)
+            const NormalsDev N = nrm_arg(nrm...);
+            n[0] = N.nsx[i]; n[1] = N.nsy[i]; n[2] = N.nsz[i];
+            if (N.strict) {
+                const float ng[3] = {N.ngx[i], N.ngy[i], N.ngz[i]};
+                if (dot3(wi, ng) * dot3(wi, n) < 0.0f) live = false;
+            }
+        }
         const float* rho = S.refl + 3 * qb;
         const float* bp = S.bpar ? S.bpar + kBsdfParams * qb : nullptr;
         const int kind = bp ? (int)bp[0] : kBsdfDiffuse;
@@ -418,9 +470,9 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
 // bsdfs/diffuse.cpp:86-92; a rough conductor or a Phong BSDF: the query's own
 // row of the extended table, its learned model conditioned here) and the
 // BSDF/guide draw.
-template <bool PHONG, bool DIEL, bool MESH>
+template <bool PHONG, bool DIEL, bool MESH, class... Nrm>
 __global__ void __launch_bounds__(256)
-li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict__ count, int product) {
+li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict__ count, int product, Nrm... nrm) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= *count) return;
     const int i = Q.idx[j];
@@ -430,7 +482,8 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
     Q.k_mode[j] = Q.mode[i];
     Q.slot[i] = j;
     if (product) {
-        const float* pn = prim_n<MESH>(S, P.quad[i]);
+        float nbuf[3];
+        const float* pn = path_ns<MESH>(S, i, P.quad[i], nbuf, nrm...);   // (NRM: F = [s t +-ns])
         const int qb = prim_bsdf<MESH>(S, P.quad[i]);
         float s[3], t[3];
         frame_of(pn, s, t);
@@ -523,17 +576,26 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
 // ENV: the variant for a scene with an environment emitter, as the camera
 // kernel's: a bounce ray that hits nothing brings evalEnvironment(wo) into
 // `value` (rayIntersectAndLookForEmitter, :1047-1051) and the path ends.
-template <bool PHONG, bool DIEL, bool MESH, bool ENV>
+// NRM: the variant for a mesh with vertex normals: the bounce runs on the
+// hit's shading normal ns; strictNormals' second test is (wo . ng)
+// cosTheta(bRec.wo) <= 0 (:777-780) with bRec.wo in its.shFrame -- twosided.cpp
+// hands wo back with its z flipped again (:137) -- so (wo . ng)(wo . ns)
+// whatever the side; without strictNormals neither test runs.  The new hit's
+// ns / ng are worked out after the trace and left in the path's planes.
+template <bool PHONG, bool DIEL, bool MESH, bool ENV, class... Nrm>
 __global__ void __launch_bounds__(256)
 li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int rr_depth, float h,
-                uint64_t seed, int product) {
+                uint64_t seed, int product, Nrm... nrm) {
+    constexpr bool NRM = sizeof...(Nrm) != 0;
+    static_assert(!NRM || MESH, "NRM: a MESH variant");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.P) return;
     int depth = P.depth[i];
     if (depth < 0) return;
     LI_MESH_STACK(stack)
     const int pq = P.quad[i];
-    const float* qn = prim_n<MESH>(S, pq);
+    float nbuf[3];
+    const float* qn = path_ns<MESH>(S, i, pq, nbuf, nrm...);
     float n[3] = {qn[0], qn[1], qn[2]};
     // a two-sided BSDF met from behind: n is the effective normal -n from here
     // on (cosines, the saved vertex); the tangents stay Frame(qn)'s
@@ -691,7 +753,13 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     }
     const float cos_o = dot3(wo, n);
     // zero weight, or strict normals (wo . n_geo * cos(wo) <= 0, :777-780): the path ends
-    if ((weight[0] == 0.0f && weight[1] == 0.0f && weight[2] == 0.0f) || !(cos_o * cos_o > 0.0f) ||
+    bool leak = !(cos_o * cos_o > 0.0f);
+    if constexpr (NRM) {
+        const NormalsDev N = nrm_arg(nrm...);
+        const float ng[3] = {N.ngx[i], N.ngy[i], N.ngz[i]};
+        leak = N.strict && !(dot3(wo, ng) * dot3(wo, qn) > 0.0f);
+    }
+    if ((weight[0] == 0.0f && weight[1] == 0.0f && weight[2] == 0.0f) || leak ||
         !__builtin_isfinite(weight[0] + weight[1] + weight[2])) {
         P.depth[i] = -1;
         return;
@@ -702,9 +770,17 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     float t;
     const int q = intersect<MESH>(S, o, wo, kEpsilon, INFINITY, t, stack);
     float value[3] = {0.0f, 0.0f, 0.0f};
+    float hns[3], hng[3];               // the new hit's normals (NRM)
     if (q >= 0) {
         const int he = prim_emitter<MESH>(S, q);
-        if (he >= 0 && -dot3(wo, prim_n<MESH>(S, q)) > 0.0f)
+        const float* hn;
+        if constexpr (NRM) {
+            hit_normals(S, nrm_arg(nrm...).shade, q, o, wo, hns, hng);
+            hn = hns;
+        } else {
+            hn = prim_n<MESH>(S, q);
+        }
+        if (he >= 0 && -dot3(wo, hn) > 0.0f)
             for (int ch = 0; ch < 3; ++ch) value[ch] = S.rad[3 * he + ch];
     }
     if constexpr (ENV)
@@ -755,6 +831,7 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     if (live) {
         P.px[i] = o[0] + t * wo[0]; P.py[i] = o[1] + t * wo[1]; P.pz[i] = o[2] + t * wo[2];
         P.quad[i] = q;
+        if constexpr (NRM) store_normals(nrm_arg(nrm...), i, hns, hng);
     }
     P.depth[i] = live ? depth + 1 : -1;
 }
@@ -933,17 +1010,36 @@ static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256)
 #define LI_VARIANT_E(kernel, S, E) \
     ((S).has_mesh ? LI_VARIANT_ME(kernel, S, true, E) : LI_VARIANT_ME(kernel, S, false, E))
 
-hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, int64_t path0, int spp, uint64_t seed,
-                            hipStream_t st) {
+// the NRM variants of a mesh with vertex normals (N.shade set): MESH, the pack {NormalsDev}
+#define LI_VARIANT_N(kernel, S)                                                                              \
+    ((S).has_dielectric ? ((S).has_phong ? kernel<true, true, true, NormalsDev> : kernel<false, true, true, NormalsDev>) \
+                        : ((S).has_phong ? kernel<true, false, true, NormalsDev> : kernel<false, false, true, NormalsDev>))
+#define LI_VARIANT_NE(kernel, S, E)                                                 \
+    ((S).has_dielectric ? ((S).has_phong ? kernel<true, true, true, E, NormalsDev>   \
+                                         : kernel<false, true, true, E, NormalsDev>) \
+                        : ((S).has_phong ? kernel<true, false, true, E, NormalsDev>  \
+                                         : kernel<false, false, true, E, NormalsDev>))
+
+hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, const NormalsDev& N, int64_t path0, int spp,
+                            uint64_t seed, hipStream_t st) {
+    if (N.shade) {
+        auto nrm = S.env.kind != kEnvNone ? li_camera_kernel<true, true, NormalsDev> : li_camera_kernel<true, false, NormalsDev>;
+        hipLaunchKernelGGL(nrm, grid_for(P.P), dim3(256), 0, st, S, P, path0, spp, seed, N);
+        return hipGetLastError();
+    }
     auto kernel = S.env.kind != kEnvNone ? (S.has_mesh ? li_camera_kernel<true, true> : li_camera_kernel<false, true>)
                                          : (S.has_mesh ? li_camera_kernel<true, false> : li_camera_kernel<false, false>);
     hipLaunchKernelGGL(kernel, grid_for(P.P), dim3(256), 0, st, S, P, path0, spp, seed);
     return hipGetLastError();
 }
-hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
-                           int max_depth, int guided, float h, uint64_t seed, hipStream_t st) {
-    hipLaunchKernelGGL(LI_VARIANT(li_query_kernel, S), grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce,
-                       max_depth, guided, h, seed);
+hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N, int64_t path0,
+                           int bounce, int max_depth, int guided, float h, uint64_t seed, hipStream_t st) {
+    if (N.shade)
+        hipLaunchKernelGGL(LI_VARIANT_N(li_query_kernel, S), grid_for(P.P), dim3(256), 0, st, S, P, Q, path0,
+                           bounce, max_depth, guided, h, seed, N);
+    else
+        hipLaunchKernelGGL(LI_VARIANT(li_query_kernel, S), grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce,
+                           max_depth, guided, h, seed);
     return hipGetLastError();
 }
 size_t li_select_temp_bytes(int64_t n) {
@@ -953,18 +1049,29 @@ size_t li_select_temp_bytes(int64_t n) {
     return b;
 }
 // live guided queries -> compact planes; *count_dev = their number
-hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t n, int32_t* count_dev,
-                             void* temp, size_t temp_bytes, int product, hipStream_t st) {
+hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N, int64_t n,
+                             int32_t* count_dev, void* temp, size_t temp_bytes, int product, hipStream_t st) {
     hipError_t e = hipcub::DeviceSelect::Flagged(temp, temp_bytes, hipcub::CountingInputIterator<int32_t>(0), Q.live,
                                                  Q.idx, count_dev, (int)n, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(LI_VARIANT(li_compact_kernel, S), grid_for(n), dim3(256), 0, st, S, P, Q,
-                       (const int32_t*)count_dev, product);
+    if (N.shade)
+        hipLaunchKernelGGL(LI_VARIANT_N(li_compact_kernel, S), grid_for(n), dim3(256), 0, st, S, P, Q,
+                           (const int32_t*)count_dev, product, N);
+    else
+        hipLaunchKernelGGL(LI_VARIANT(li_compact_kernel, S), grid_for(n), dim3(256), 0, st, S, P, Q,
+                           (const int32_t*)count_dev, product);
     return hipGetLastError();
 }
 
-hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, int64_t path0, int bounce,
-                           int rr_depth, float h, uint64_t seed, int product, hipStream_t st) {
+hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N, int64_t path0,
+                           int bounce, int rr_depth, float h, uint64_t seed, int product, hipStream_t st) {
+    if (N.shade) {
+        auto nrm = S.env.kind != kEnvNone ? LI_VARIANT_NE(li_shade_kernel, S, true)
+                                          : LI_VARIANT_NE(li_shade_kernel, S, false);
+        hipLaunchKernelGGL(nrm, grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce, rr_depth, h, seed, product,
+                           N);
+        return hipGetLastError();
+    }
     auto kernel = S.env.kind != kEnvNone ? LI_VARIANT_E(li_shade_kernel, S, true) : LI_VARIANT_E(li_shade_kernel, S, false);
     hipLaunchKernelGGL(kernel, grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce, rr_depth, h, seed, product);
     return hipGetLastError();
@@ -1198,6 +1305,51 @@ hipError_t launch_scene_intersect(const SceneDev& S, int64_t nq, const float* co
     else
         hipLaunchKernelGGL(scene_intersect_kernel<true>, grid_for(nq), dim3(256), 0, st, S, nq, o[0], o[1], o[2],
                            d[0], d[1], d[2], mint, maxt, prim, t);
+    return hipGetLastError();
+}
+
+// sdmm_scene_shading: sdmm_scene_intersect's search, then the hit's shading
+// and geometric normal as the Li kernels compute them (hit_normals); zeros on
+// a miss
+template <bool BRUTE>
+__global__ void __launch_bounds__(256)
+scene_shading_kernel(SceneDev S, const MeshShade* __restrict__ shade, int64_t nq, const float* __restrict__ o0, const float* __restrict__ o1,
+                     const float* __restrict__ o2, const float* __restrict__ d0, const float* __restrict__ d1,
+                     const float* __restrict__ d2, float mint, float maxt, int32_t* __restrict__ prim,
+                     float* __restrict__ t_out, float* __restrict__ ns0, float* __restrict__ ns1,
+                     float* __restrict__ ns2, float* __restrict__ ng0, float* __restrict__ ng1,
+                     float* __restrict__ ng2) {
+    __shared__ int bvh_lds[BRUTE ? 1 : kBvhStack * 256];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const float o[3] = {o0[i], o1[i], o2[i]}, d[3] = {d0[i], d1[i], d2[i]};
+    float t;
+    int best = quads_closest(S.quads, S.n_quads, o, d, mint, maxt, t);
+    if (S.n_tris > 0) {
+        if (BRUTE) {
+            mesh_brute(S.tris, S.n_tris, S.n_quads, o, d, mint, maxt, best, t);
+        } else {
+            LdsStack st{bvh_lds + threadIdx.x};
+            bvh_closest(S.nodes, S.tris, S.n_quads, o, d, mint, maxt, best, t, st);
+        }
+    }
+    float ns[3] = {0.0f, 0.0f, 0.0f}, ng[3] = {0.0f, 0.0f, 0.0f};
+    if (best >= 0) hit_normals(S, shade, best, o, d, ns, ng);
+    prim[i] = best;
+    t_out[i] = t;
+    ns0[i] = ns[0]; ns1[i] = ns[1]; ns2[i] = ns[2];
+    ng0[i] = ng[0]; ng1[i] = ng[1]; ng2[i] = ng[2];
+}
+hipError_t launch_scene_shading(const SceneDev& S, const MeshShade* shade, int64_t nq, const float* const o[3],
+                                const float* const d[3], float mint, float maxt, int mode, int32_t* prim, float* t,
+                                float* const ns[3], float* const ng[3], hipStream_t st) {
+    if (nq <= 0) return hipSuccess;
+    if (mode == 0)
+        hipLaunchKernelGGL(scene_shading_kernel<false>, grid_for(nq), dim3(256), 0, st, S, shade, nq, o[0], o[1],
+                           o[2], d[0], d[1], d[2], mint, maxt, prim, t, ns[0], ns[1], ns[2], ng[0], ng[1], ng[2]);
+    else
+        hipLaunchKernelGGL(scene_shading_kernel<true>, grid_for(nq), dim3(256), 0, st, S, shade, nq, o[0], o[1],
+                           o[2], d[0], d[1], d[2], mint, maxt, prim, t, ns[0], ns[1], ns[2], ng[0], ng[1], ng[2]);
     return hipGetLastError();
 }
 

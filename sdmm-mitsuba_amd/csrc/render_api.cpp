@@ -42,6 +42,7 @@ struct sdmm_scene {
     BvhNode* dnodes = nullptr;   // the triangle mesh (mesh_bvh.h), null without one
     MeshTri* dtris = nullptr;
     MeshHit* dhits = nullptr;
+    MeshShade* dshade = nullptr;   // the mesh's vertex normals (shading_normal.h), null without them
     EnvTexel* denv = nullptr;    // the lat-long environment map (envmap.h), null without one
     float smin[3] = {0, 0, 0}, snorm = 1.0f, tmin[3] = {0, 0, 0}, tmax[3] = {0, 0, 0};
     // per-render buffers (grown)
@@ -51,6 +52,7 @@ struct sdmm_scene {
     int cap_v = 0;
     PathsDev P{};
     QueryDev Q{};
+    NormalsDev N{};   // (vertex normals: N.shade = dshade, the ns / ng planes in buf)
     int64_t* dsum = nullptr;
     int32_t* dcount = nullptr;   // live guided queries of the current bounce
     int32_t* hcount = nullptr;   // (pinned host copy)
@@ -88,6 +90,7 @@ float dot3h(const float a[3], const float b[3]) { return a[0] * b[0] + a[1] * b[
 int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
     if (P <= s->cap_paths && V <= s->cap_v && s->buf) return SDMM_OK;
     const bool diel = s->S.has_dielectric != 0;   // (the eta planes: only with a dielectric or a kind-5 / 6 BSDF)
+    const bool nrm = s->N.shade != nullptr;       // (the ns / ng planes: only with vertex normals)
     const int64_t cap = std::max<int64_t>(P, s->cap_paths);
     const int cv = std::max(V, s->cap_v);
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
@@ -97,7 +100,7 @@ int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
     (void)hipcub::DeviceReduce::Sum(nullptr, tb, (const int32_t*)nullptr, (int64_t*)nullptr, (int)cap);
     tb = std::max(tb, li_select_temp_bytes(cap));
     const size_t need = 12 * f + 4 * i4 + recb + 13 * f + u1 + i4 + 256 + al(tb) + 9 * f + 2 * u1 + 3 * i4 +
-                        (1 + 1 + 9 + 1) * f + i4 + u1 + 4 * f + (diel ? 2 * f : 0);
+                        (1 + 1 + 9 + 1) * f + i4 + u1 + 4 * f + (diel ? 2 * f : 0) + (nrm ? 6 * f : 0);
     HIP_TRY(hipStreamSynchronize(st));
     if (s->buf) HIP_TRY(hipFree(s->buf));
     s->buf = nullptr;
@@ -141,6 +144,8 @@ int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
     for (float** q : bf) *q = (float*)take(f);
     s->P.eta = diel ? (float*)take(f) : nullptr;
     s->Q.beta = diel ? (float*)take(f) : nullptr;
+    float** nf[6] = {&s->N.nsx, &s->N.nsy, &s->N.nsz, &s->N.ngx, &s->N.ngy, &s->N.ngz};
+    for (float** q : nf) *q = nrm ? (float*)take(f) : nullptr;
     return SDMM_OK;
 }
 
@@ -260,6 +265,7 @@ int prep_twosided(const sdmm_scene_desc* d, const char* who, bool* any) {
 int prep_quads(const sdmm_scene_desc* d, const char* who, std::vector<QuadDev>* qs, float mn[3], float mx[3]) {
     const std::string w(who);
     if (!geometry_args_ok(d)) return fail(SDMM_E_INVALID, w + ": invalid description");
+    if (d->mesh_normals && d->n_triangles < 1) return fail(SDMM_E_INVALID, w + ": mesh_normals without triangles");
     if (const int rc = prep_twosided(d, who, nullptr)) return rc;
     if (has_emitters(d) && (d->n_emitters < 1 || !d->radiance))
         return fail(SDMM_E_INVALID, w + ": emitters without radiance");
@@ -306,6 +312,7 @@ int prep_mesh(const sdmm_scene_desc* d, const char* who, int max_levels, MeshBvh
     in.bsdf = d->tri_bsdf;
     in.emitter = d->tri_emitter;
     in.flip = d->tri_flip_normals;
+    in.normals = d->mesh_normals;
     in.n_bsdfs = d->n_bsdfs;
     in.n_emitters = d->n_emitters;
     std::string err;
@@ -482,6 +489,9 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
         e = hipMemcpy(s->dtris, mesh.tris.data(), sizeof(MeshTri) * mesh.tris.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess && d->n_triangles > 0)
         e = hipMemcpy(s->dhits, mesh.hits.data(), sizeof(MeshHit) * mesh.hits.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !mesh.shade.empty()) e = hipMalloc(&s->dshade, sizeof(MeshShade) * mesh.shade.size());
+    if (e == hipSuccess && !mesh.shade.empty())
+        e = hipMemcpy(s->dshade, mesh.shade.data(), sizeof(MeshShade) * mesh.shade.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess && !env_texels.empty()) e = hipMalloc(&s->denv, sizeof(EnvTexel) * env_texels.size());
     if (e == hipSuccess && !env_texels.empty())
         e = hipMemcpy(s->denv, env_texels.data(), sizeof(EnvTexel) * env_texels.size(), hipMemcpyHostToDevice);
@@ -522,6 +532,7 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     S.nodes = s->dnodes;
     S.tris = s->dtris;
     S.hits = s->dhits;
+    s->N.shade = s->dshade;
     S.n_tris = d->n_triangles;
     S.has_mesh = d->n_triangles > 0 ? 1 : 0;
     {
@@ -765,6 +776,7 @@ void sdmm_scene_destroy(sdmm_scene* s) {
     if (s->dnodes) (void)hipFree(s->dnodes);
     if (s->dtris) (void)hipFree(s->dtris);
     if (s->dhits) (void)hipFree(s->dhits);
+    if (s->dshade) (void)hipFree(s->dshade);
     if (s->denv) (void)hipFree(s->denv);
     if (s->buf) (void)hipFree(s->buf);
     if (s->lt) (void)hipFree(s->lt);
@@ -825,6 +837,56 @@ int sdmm_scene_intersect_host_levels(const sdmm_scene_desc* desc, int max_levels
         if (desc->n_triangles > 0) mesh_closest_host(mesh, nquads, mode, o + 3 * i, d + 3 * i, mint, maxt, best, tb);
         prim[i] = best;
         t[i] = tb;
+    }
+    _mm_setcsr(csr);
+    return SDMM_OK;
+}
+
+int sdmm_scene_shading(const sdmm_scene* s, int64_t nq, const float* const o[3], const float* const d[3], float mint,
+                       float maxt, int mode, int32_t* prim, float* t, float* const ns[3], float* const ng[3],
+                       void* hip_stream) {
+    if (!s || nq < 0 || (mode != 0 && mode != 1))
+        return fail(SDMM_E_INVALID, "sdmm_scene_shading: invalid argument (mode 0 or 1)");
+    if (nq == 0) return SDMM_OK;
+    if (!o || !o[0] || !o[1] || !o[2] || !d || !d[0] || !d[1] || !d[2] || !prim || !t || !ns || !ns[0] || !ns[1] ||
+        !ns[2] || !ng || !ng[0] || !ng[1] || !ng[2])
+        return fail(SDMM_E_INVALID, "sdmm_scene_shading: NULL plane");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(launch_scene_shading(s->S, s->N.shade, nq, o, d, mint, maxt, mode, prim, t, ns, ng, (hipStream_t)hip_stream));
+    return SDMM_OK;
+}
+
+int sdmm_scene_shading_host(const sdmm_scene_desc* desc, int64_t nq, const float* o, const float* d, float mint,
+                            float maxt, int mode, int32_t* prim, float* t, float* ns, float* ng) {
+    if (!desc || nq < 0 || (mode != 0 && mode != 1) || (nq > 0 && (!o || !d || !prim || !t || !ns || !ng)))
+        return fail(SDMM_E_INVALID, "sdmm_scene_shading_host: invalid argument (mode 0 or 1)");
+    std::vector<QuadDev> qs;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    int rc = prep_quads(desc, "sdmm_scene_shading_host", &qs, mn, mx);
+    if (rc) return rc;
+    MeshBvh mesh;
+    if (desc->n_triangles > 0) {
+        rc = prep_mesh(desc, "sdmm_scene_shading_host", 0, &mesh);
+        if (rc) return rc;
+    }
+    // the scene as hit_normals reads it, on host arrays
+    SceneDev S{};
+    S.quads = qs.data();
+    S.n_quads = (int)qs.size();
+    S.hits = mesh.hits.data();
+    const MeshShade* shade = mesh.shade.empty() ? nullptr : mesh.shade.data();
+    // the device's float environment: denormals flushed (-fgpu-flush-denormals-to-zero)
+    const unsigned csr = _mm_getcsr();
+    _mm_setcsr(csr | 0x8040u);
+    for (int64_t i = 0; i < nq; ++i) {
+        float tb;
+        int best = quads_closest(qs.data(), S.n_quads, o + 3 * i, d + 3 * i, mint, maxt, tb);
+        if (desc->n_triangles > 0)
+            mesh_closest_host(mesh, S.n_quads, mode, o + 3 * i, d + 3 * i, mint, maxt, best, tb);
+        prim[i] = best;
+        t[i] = tb;
+        for (int a = 0; a < 3; ++a) ns[3 * i + a] = ng[3 * i + a] = 0.0f;
+        if (best >= 0) hit_normals(S, shade, best, o + 3 * i, d + 3 * i, ns + 3 * i, ng + 3 * i);
     }
     _mm_setcsr(csr);
     return SDMM_OK;
@@ -910,6 +972,7 @@ int sdmm_li_render(sdmm_scene* s, sdmm_stree* t, const sdmm_mix* const* node_mix
     if (r) return r;
     s->P.V = V;
     s->P.P = P;
+    s->N.strict = p->non_strict_normals ? 0 : 1;
     sdmm_bsdf_table ltab{};
     s->Q.lw = s->Q.lm = s->Q.lc = nullptr;
     if (product && p->guided && s->per_query_lobes) {
@@ -917,7 +980,7 @@ int sdmm_li_render(sdmm_scene* s, sdmm_stree* t, const sdmm_mix* const* node_mix
         if (r) return r;
     }
     const int64_t path0 = p->pixel_begin * p->spp;
-    HIP_TRY(launch_li_camera(s->S, s->P, path0, p->spp, p->seed, st));
+    HIP_TRY(launch_li_camera(s->S, s->P, s->N, path0, p->spp, p->seed, st));
     // bounces: rRec.depth 1 .. maxDepth - 1 scatter (:649, :684); unbounded
     // paths stop at the vertex slots
     const int bounces = p->max_depth > 0 ? p->max_depth - 1 : V;
@@ -934,12 +997,12 @@ int sdmm_li_render(sdmm_scene* s, sdmm_stree* t, const sdmm_mix* const* node_mix
         for (int b = 0; b < bounces; ++b) s->hfb[b] = 0;
     const float h = p->bsdf_fraction;
     for (int b = 0; b < bounces; ++b) {
-        HIP_TRY(launch_li_query(s->S, s->P, s->Q, path0, b, p->max_depth > 0 ? p->max_depth : INT32_MAX, p->guided,
+        HIP_TRY(launch_li_query(s->S, s->P, s->Q, s->N, path0, b, p->max_depth > 0 ? p->max_depth : INT32_MAX, p->guided,
                                 h, p->seed, st));
         if (p->guided) {
             // only the live paths query the guide: compact them (the order of
             // the compact queries does not change any query's outputs)
-            HIP_TRY(launch_li_compact(s->S, s->P, s->Q, P, s->dcount, s->temp, s->temp_bytes, product, st));
+            HIP_TRY(launch_li_compact(s->S, s->P, s->Q, s->N, P, s->dcount, s->temp, s->temp_bytes, product, st));
             HIP_TRY(hipMemcpyAsync(s->hcount, s->dcount, sizeof(int32_t), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             const int64_t nlive = *s->hcount;
@@ -970,7 +1033,7 @@ int sdmm_li_render(sdmm_scene* s, sdmm_stree* t, const sdmm_mix* const* node_mix
             }
             guided_queries += nlive;
         }
-        HIP_TRY(launch_li_shade(s->S, s->P, s->Q, path0, b, p->rr_depth, h, p->seed, product && p->guided, st));
+        HIP_TRY(launch_li_shade(s->S, s->P, s->Q, s->N, path0, b, p->rr_depth, h, p->seed, product && p->guided, st));
     }
     HIP_TRY(launch_li_film(s->P, p->pixel_begin, npix, p->spp, npix_all, image, image_sqr, st));
     if (vout) {

@@ -93,6 +93,39 @@ struct SceneDev {
     const int32_t* twosided;
 };
 
+// What only the NRM variants of the Li kernels read (a mesh with vertex
+// normals, shading_normal.h): a record of its own, passed after every other
+// kernel argument, so that SceneDev, PathsDev and the argument layout of the
+// variants every other scene runs stay what they were.
+struct NormalsDev {
+    // the mesh's vertex normals by triangle index; null: none, every hit's
+    // shading and geometric normal is its face normal
+    const MeshShade* shade;
+    // the current hit's shading and geometric normal, one plane a component:
+    // written by the kernel that traced the ray (camera, shade), read by the
+    // next bounce's kernels; null without vertex normals
+    float *nsx, *nsy, *nsz;
+    float *ngx, *ngy, *ngz;
+    int strict;              // strictNormals of this render (sdmm_li_params.non_strict_normals == 0)
+};
+
+// the shading normal ns and the geometric normal ng of the hit of the ray (o,
+// d) on primitive q, as sdmm_scene_shading reports them: a triangle with
+// vertex normals through shading_normals, anything else its face normal twice
+__host__ __device__ __forceinline__ void hit_normals(const SceneDev& S, const MeshShade* shade, int q,
+                                                     const float o[3], const float d[3], float ns[3], float ng[3]) {
+    if (q >= S.n_quads) {
+        const int ti = q - S.n_quads;
+        if (shade) {
+            shading_normals(shade[ti], S.hits[ti].n, o, d, ns, ng);
+            return;
+        }
+        for (int a = 0; a < 3; ++a) ns[a] = ng[a] = S.hits[ti].n[a];
+        return;
+    }
+    for (int a = 0; a < 3; ++a) ns[a] = ng[a] = S.quads[q].n[a];
+}
+
 // a hit from behind (cos_i = wi . n < 0) on a two-sided BSDF: the bounce runs
 // in (s, t, -n) of Frame(n) (wi.z *= -1 ... wo.z *= -1, twosided.cpp:111-137,
 // :191-213) and the saved vertex carries -n (sdmm_proc.cpp:765-767)

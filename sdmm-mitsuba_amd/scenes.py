@@ -371,19 +371,55 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
     }
 
 
-def torus_mesh(nu, nv, R=1.0, r=0.4, to_world=None):
+def vertex_normals(vertices, triangles):
+    """Mitsuba's computeNormals (librender/trimesh.cpp:636-672; Thuermer and
+    Wuethrich, "Computing Vertex Normals from Polygonal Facets"): each
+    triangle's unit face normal added to its three vertices weighted by the
+    triangle's angle there, the sums normalised -- in float64, returned as
+    float32 [n_vertices, 3].  A zero-area triangle adds nothing; a vertex no
+    triangle reaches gets Mitsuba's bogus (1, 0, 0)."""
+    V = np.asarray(vertices, np.float64).reshape(-1, 3)
+    T = np.asarray(triangles, np.int64).reshape(-1, 3)
+    N = np.zeros_like(V)
+    p = V[T]                                                    # [nt, 3, 3]
+    fn = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    fl = np.linalg.norm(fn, axis=1)
+    ok = fl > 0
+    fn[ok] /= fl[ok, None]
+    for k in range(3):
+        a, b = p[:, (k + 1) % 3] - p[:, k], p[:, (k + 2) % 3] - p[:, k]
+        la, lb = np.linalg.norm(a, axis=1), np.linalg.norm(b, axis=1)
+        good = ok & (la > 0) & (lb > 0)
+        cos = np.zeros(len(T))
+        cos[good] = np.einsum("ij,ij->i", a[good], b[good]) / (la[good] * lb[good])
+        angle = np.where(good, np.arccos(np.clip(cos, -1.0, 1.0)), 0.0)
+        np.add.at(N, T[:, k], fn * angle[:, None])
+    ln = np.linalg.norm(N, axis=1)
+    bad = ~(ln > 0)
+    N[~bad] /= ln[~bad, None]
+    N[bad] = (1.0, 0.0, 0.0)
+    return N.astype(np.float32)
+
+
+def torus_mesh(nu, nv, R=1.0, r=0.4, to_world=None, normals=False):
     """A torus about the y axis (centre circle of radius R in the xz plane,
     tube radius r) as nu x nv quads of two triangles: (vertices [nu * nv, 3]
     float32, triangles [2 * nu * nv, 3] int32), counter-clockwise seen from
-    outside.  to_world: a 3x4 or 4x4 matrix applied to the vertices."""
+    outside.  to_world: a 3x4 or 4x4 matrix applied to the vertices.
+    normals: also the analytic unit outward normals at the vertices (float32
+    [nu * nv, 3], third of the tuple), through to_world's inverse transpose
+    and normalised again."""
     u = 2.0 * np.pi * np.arange(nu) / nu
     v = 2.0 * np.pi * np.arange(nv) / nv
     uu, vv = np.meshgrid(u, v, indexing="ij")
     ring = R + r * np.cos(vv)
     P = np.stack([ring * np.cos(uu), r * np.sin(vv), ring * np.sin(uu)], -1).reshape(-1, 3)
+    Nn = np.stack([np.cos(vv) * np.cos(uu), np.sin(vv), np.cos(vv) * np.sin(uu)], -1).reshape(-1, 3)
     if to_world is not None:
         M = np.asarray(to_world, np.float64).reshape(-1, 4)[:3]
         P = P @ M[:, :3].T + M[:, 3]
+        Nn = Nn @ np.linalg.inv(M[:, :3])       # rows times (A^-T)^T
+        Nn /= np.linalg.norm(Nn, axis=1, keepdims=True)
     i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
     a = (i * nv + j).reshape(-1)
     b = (((i + 1) % nu) * nv + j).reshape(-1)
@@ -393,6 +429,8 @@ def torus_mesh(nu, nv, R=1.0, r=0.4, to_world=None):
     tris = np.concatenate([np.stack([a, d, c], -1), np.stack([a, c, b], -1)], 1).reshape(-1, 3)
     if to_world is not None and np.linalg.det(M[:, :3]) < 0:
         tris = tris[:, ::-1]
+    if normals:
+        return P.astype(np.float32), np.ascontiguousarray(tris, np.int32), Nn.astype(np.float32)
     return P.astype(np.float32), np.ascontiguousarray(tris, np.int32)
 
 
@@ -486,7 +524,8 @@ def sky_environment(width=256, height=128, sun_dir=(0.35, 0.8, 0.45), sun_radius
             "env_world_to_local": np.linalg.inv(R).astype(np.float32).reshape(-1)}
 
 
-def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=None, smooth=False):
+def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=None, smooth=False,
+                smooth_normals=False):
     """The Torus configuration's stand-in (test-suite/scenes/torus/torus.xml):
     a diffuse torus (reflectance .8, .8, .4; torus_mesh(nu, nv), R 1, r 0.4,
     lying on the floor) under a rough-dielectric case of quads (alpha 0.05,
@@ -504,7 +543,10 @@ def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=Non
     ring each at opposite sides of it, smooth conductors
     (kind 6: its `conductor`) with a gray eta / k near aluminium's (1.2, 7.0);
     the reference's spectral .spd data of the metal is not used.  The rest of
-    the torus stays diffuse.  False (the default): the scene as it was."""
+    the torus stays diffuse.  False (the default): the scene as it was.
+    smooth_normals: the torus carries its analytic vertex normals
+    (mesh_normals): shaded, trained and guided as the curved surface it
+    stands for.  False (the default): face normals, the scene as it was."""
     names = ["Room", "Floor", "Torus", "Glass", "Light"] + (["Metal"] if smooth else [])
     refl = {"Room": (0.6, 0.6, 0.6), "Floor": (0.5, 0.5, 0.5), "Torus": (0.8, 0.8, 0.4), "Glass": (1.0, 1.0, 1.0),
             "Light": (0.0, 0.0, 0.0), "Metal": (0.0, 0.0, 0.0)}
@@ -541,7 +583,9 @@ def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=Non
             model = load_learned_nd(LEARNED_DIELECTRIC)
             extra["learned_models_nd"] = [model if nm == "Glass" else None for nm in names]
     T = np.array([[1.0, 0, 0, 0], [0, 1.0, 0, 0.45], [0, 0, 1.0, 0]])
-    verts, tris = torus_mesh(nu, nv, 1.0, 0.4, to_world=T)
+    verts, tris, vnrm = torus_mesh(nu, nv, 1.0, 0.4, to_world=T, normals=True)
+    if smooth_normals:
+        extra["mesh_normals"] = vnrm.reshape(-1)
     tri_bsdf = np.full(len(tris), names.index("Torus"), np.int32)
     if smooth:
         # torus_mesh orders its triangles by the ring index: two opposite arcs of an eighth of the ring each
@@ -568,11 +612,14 @@ def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=Non
     }
 
 
-def sheet_mesh(nx, nz, x=(-1.8, 1.8), z=(1.4, -2.6), y0=1.6, amplitude=0.45, waves=1.25, phase=np.pi):
+def sheet_mesh(nx, nz, x=(-1.8, 1.8), z=(1.4, -2.6), y0=1.6, amplitude=0.45, waves=1.25, phase=np.pi,
+               normals=False):
     """An open sheet: the height field y = y0 + amplitude sin(2 pi waves s +
     phase) over x[0]..x[1] and, along s in [0, 1], z[0]..z[1], as nx x nz
     cells of two triangles with the face normals on the +y side: (vertices
-    [(nx + 1)(nz + 1), 3] float32, triangles [2 nx nz, 3] int32)."""
+    [(nx + 1)(nz + 1), 3] float32, triangles [2 nx nz, 3] int32).  normals:
+    also the height field's analytic unit normals at the vertices, on the +y
+    side (float32, third of the tuple)."""
     a = np.linspace(0.0, 1.0, nx + 1)
     s = np.linspace(0.0, 1.0, nz + 1)
     aa, ss = np.meshgrid(a, s, indexing="ij")
@@ -585,6 +632,12 @@ def sheet_mesh(nx, nz, x=(-1.8, 1.8), z=(1.4, -2.6), y0=1.6, amplitude=0.45, wav
     # (dP/da) x (dP/ds) points along +y when x grows with a and z falls with s
     if (x[1] - x[0]) * (z[1] - z[0]) > 0:
         tris = tris[:, ::-1]
+    if normals:
+        # y = f(s), z = z0 + (z1 - z0) s: the normal is (0, 1, -dy/dz) normalised
+        dyds = amplitude * 2.0 * np.pi * waves * np.cos(2.0 * np.pi * waves * ss + phase)
+        Nn = np.stack([np.zeros_like(ss), np.ones_like(ss), -dyds / (z[1] - z[0])], -1).reshape(-1, 3)
+        Nn /= np.linalg.norm(Nn, axis=1, keepdims=True)
+        return P.astype(np.float32), np.ascontiguousarray(tris, np.int32), Nn.astype(np.float32)
     return P.astype(np.float32), np.ascontiguousarray(tris, np.int32)
 
 
@@ -592,7 +645,7 @@ SHEET_MATERIALS = ("diffuse", "plastic", "conductor", "phong", "mirror")   # kin
 
 
 def sheet_scene(width=640, height=360, nx=16, nz=48, material="diffuse", twosided=True, environment=None,
-                reflectance=(0.7, 0.6, 0.4), learned=True, patch=False):
+                reflectance=(0.7, 0.6, 0.4), learned=True, patch=False, smooth_normals=False):
     """An open surface for the `twosided` adapter: torus_scene's lit room (or,
     with environment=, its open floor under that sky) holding a sheet --
     sheet_mesh(nx, nz), a sine wave hanging at the camera's height and running
@@ -607,7 +660,8 @@ def sheet_scene(width=640, height=360, nx=16, nz=48, material="diffuse", twoside
     patch: a two-sided rough-conductor quad (alpha 0.2, its learned SDMM4)
     lying face up above the sheet and the camera: what reaches it from below
     meets its back, and in the open scene (environment=) nothing lies above
-    it, so every hit on it is one from behind."""
+    it, so every hit on it is one from behind.  smooth_normals: the sheet
+    carries its analytic vertex normals (mesh_normals)."""
     if material not in SHEET_MATERIALS:
         raise ValueError(f"material: one of {SHEET_MATERIALS}")
     names = ["Room", "Floor", "Sheet", "Light"] + (["Patch"] if patch else [])
@@ -657,7 +711,9 @@ def sheet_scene(width=640, height=360, nx=16, nz=48, material="diffuse", twoside
         extra["bsdf_twosided"] = np.asarray([int(nm in ("Sheet", "Patch")) for nm in names], np.int32)
     if environment is not None:
         extra.update(environment)
-    verts, tris = sheet_mesh(nx, nz)
+    verts, tris, vnrm = sheet_mesh(nx, nz, normals=True)
+    if smooth_normals:
+        extra["mesh_normals"] = vnrm.reshape(-1)
     return {**extra,
         "quads": np.asarray(quads, np.float32).reshape(-1),
         "bsdf": np.asarray(bsdf, np.int32),
@@ -684,7 +740,16 @@ def mirror_z(desc, keep=()):
     index) -- the mirror reverses a primitive's winding, so toggling keeps its
     normal the mirrored one, and a kept primitive keeps the normal it had: it
     is then met from the other side.  Order and every other field are the
-    same; the environment's transform is not mirrored."""
+    same; the environment's transform is not mirrored.
+    With mesh_normals their z is negated too, and the triangles' rule turns
+    round: the flag does not undo a winding there, it negates the shading
+    normal ns itself (the winding's face normal only follows ns), so a
+    triangle's flag is left as it is -- ns is then the mirrored one, and ng,
+    whose unflipped face normal the mirror negated, is turned back onto it --
+    and a triangle listed in `keep` gets its flag toggled: ns = -mirror(ns),
+    met from the other side.  (Where the interpolated normal vanishes the
+    library falls back to the face normal with the flag applied, which this
+    rule leaves negated.)  Mirroring twice gives the description back."""
     out = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in desc.items()}
     keep = set(int(k) for k in keep)
     nq = 0
@@ -702,7 +767,14 @@ def mirror_z(desc, keep=()):
         nt = np.asarray(desc["triangles"]).size // 3
         fl = np.array(desc["tri_flip_normals"], np.int32) if desc.get("tri_flip_normals") is not None \
             else np.zeros(nt, np.int32)
-        out["tri_flip_normals"] = np.asarray([f if nq + i in keep else 1 - f for i, f in enumerate(fl)], np.int32)
+        if desc.get("mesh_normals") is not None:
+            n = np.array(desc["mesh_normals"], np.float32).reshape(-1, 3)
+            n[:, 2] = -n[:, 2]
+            out["mesh_normals"] = n.reshape(-1)
+            out["tri_flip_normals"] = np.asarray([1 - f if nq + i in keep else f for i, f in enumerate(fl)], np.int32)
+        else:
+            out["tri_flip_normals"] = np.asarray([f if nq + i in keep else 1 - f for i, f in enumerate(fl)],
+                                                 np.int32)
     cam = np.array(desc["camera_to_world"], np.float32).reshape(4, 4)
     cam[2, :] = -cam[2, :]
     out["camera_to_world"] = cam.reshape(-1)

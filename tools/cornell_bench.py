@@ -14,6 +14,9 @@
 --env              with --torus: the open scene -- no room, no lamp, the torus
                    under its case on the floor under scenes.sky_environment()
                    (a lat-long environment map)
+--smooth-normals   with --torus: the torus carries its analytic vertex normals
+                   (scenes.torus_scene(smooth_normals=True)): the Li kernels'
+                   NRM variants run
 --env-eval N       time sdmm_env_eval on 2^N random directions against a
                    1024x512 map (device time per launch from events); with
                    --repeat 0 nothing else runs
@@ -50,6 +53,7 @@ if __name__ == "__main__":
     ap.add_argument("--tess", default="96x48", help="--torus: tessellation NUxNV")
     ap.add_argument("--intersect", type=int, default=0, help="--torus: time Scene.intersect on 2^N rays")
     ap.add_argument("--env", action="store_true", help="--torus: the open scene under a sky environment map")
+    ap.add_argument("--smooth-normals", action="store_true", help="--torus: vertex normals on the torus")
     ap.add_argument("--env-eval", type=int, default=0, help="time Scene.env_eval on 2^N directions, 1024x512 map")
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--summary", action="store_true", help="one line per run, no per-iteration lines")
@@ -65,6 +69,8 @@ if __name__ == "__main__":
                                                dielectric_lift=0.02)
     if a.env and not a.torus:
         ap.error("--env goes with --torus")
+    if a.smooth_normals and not a.torus:
+        ap.error("--smooth-normals goes with --torus")
     if a.env_eval:
         import numpy as np
         scenes = importlib.import_module("sdmm_mitsuba_amd.scenes")
@@ -96,8 +102,10 @@ if __name__ == "__main__":
         scenes = importlib.import_module("sdmm_mitsuba_amd.scenes")
         nu, nv = (int(x) for x in a.tess.lower().split("x"))
         sky = scenes.sky_environment() if a.env else None
-        scenes.cornell_box = lambda w, h, **kw: (scenes.torus_scene(w, h, nu, nv, environment=sky) if a.env
-                                                 else scenes.torus_scene(w, h, nu, nv))
+        # (smooth_normals is passed only when asked for: without the flag the call is what it always was)
+        nkw = {"smooth_normals": True} if a.smooth_normals else {}
+        scenes.cornell_box = lambda w, h, **kw: (scenes.torus_scene(w, h, nu, nv, environment=sky, **nkw) if a.env
+                                                 else scenes.torus_scene(w, h, nu, nv, **nkw))
         brute = os.environ.get("SDMM_MESH_BRUTE") == "1"
         if a.intersect:
             dev = torch.device("cuda", 0)
@@ -154,7 +162,8 @@ if __name__ == "__main__":
             if a.torus:
                 out["workload"] = out["workload"].replace("Cornell Box", f"Torus scene ({a.tess}, " +
                                                           ("brute force" if brute else "BVH") +
-                                                          (", open under a sky map" if a.env else "") + ")")
+                                                          (", open under a sky map" if a.env else "") +
+                                                          (", vertex normals" if a.smooth_normals else "") + ")")
                 its = out["iterations"]
                 out["first_pass_ms"] = round(its[0]["ms"], 3)     # unguided render + push + optimize
                 out["guided_pass_ms"] = [round(x["ms"], 3) for x in its if not x["train"]]

@@ -997,49 +997,49 @@ __global__ void produce_seg_kernel(const uint32_t* __restrict__ keys, int64_t n,
 // ---------------------------------------------------------------------------
 // host launchers
 static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-// the Li kernel variant of a scene: <PHONG, DIEL> by the BSDF kinds it holds
-#define LI_VARIANT_M(kernel, S, M)                                                         \
-    ((S).has_dielectric ? ((S).has_phong ? kernel<true, true, M> : kernel<false, true, M>) \
-                        : ((S).has_phong ? kernel<true, false, M> : kernel<false, false, M>))
-#define LI_VARIANT(kernel, S) ((S).has_mesh ? LI_VARIANT_M(kernel, S, true) : LI_VARIANT_M(kernel, S, false))
-
-// the camera and shade kernels' ENV variants: a scene with an environment emitter
-#define LI_VARIANT_ME(kernel, S, M, E)                                                           \
-    ((S).has_dielectric ? ((S).has_phong ? kernel<true, true, M, E> : kernel<false, true, M, E>) \
-                        : ((S).has_phong ? kernel<true, false, M, E> : kernel<false, false, M, E>))
-#define LI_VARIANT_E(kernel, S, E) \
-    ((S).has_mesh ? LI_VARIANT_ME(kernel, S, true, E) : LI_VARIANT_ME(kernel, S, false, E))
-
-// the NRM variants of a mesh with vertex normals (N.shade set): MESH, the pack {NormalsDev}
-#define LI_VARIANT_N(kernel, S)                                                                              \
-    ((S).has_dielectric ? ((S).has_phong ? kernel<true, true, true, NormalsDev> : kernel<false, true, true, NormalsDev>) \
-                        : ((S).has_phong ? kernel<true, false, true, NormalsDev> : kernel<false, false, true, NormalsDev>))
-#define LI_VARIANT_NE(kernel, S, E)                                                 \
-    ((S).has_dielectric ? ((S).has_phong ? kernel<true, true, true, E, NormalsDev>   \
-                                         : kernel<false, true, true, E, NormalsDev>) \
-                        : ((S).has_phong ? kernel<true, false, true, E, NormalsDev>  \
-                                         : kernel<false, false, true, E, NormalsDev>))
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument
+template <class F>
+static void with_flag(bool flag, F f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+// The Li kernel variant of a scene, stated once: launch(phong, diel, mesh, env,
+// nrm...) gets, as std::bool_constant values, PHONG = some BSDF is Phong, DIEL =
+// some is a dielectric or delta only, MESH = the scene has triangles, ENV = it
+// has an environment emitter (ENV_KERNEL: the camera and shade kernels; false
+// for the others), and the pack nrm = N with vertex normals (N.shade set: the
+// NRM variants, always MESH), nothing otherwise.  (The nesting -- NRM, ENV,
+// MESH, DIEL, PHONG, true first -- is the order the variants are instantiated
+// in, and so the order of the kernels in the code object.)
+template <bool ENV_KERNEL, class F>
+static void li_variant(const SceneDev& S, const NormalsDev& N, F launch) {
+    const auto by_bsdfs = [&](auto env, auto mesh, auto... nrm) {
+        with_flag(S.has_dielectric, [&](auto diel) {
+            with_flag(S.has_phong, [&](auto phong) { launch(phong, diel, mesh, env, nrm...); });
+        });
+    };
+    const auto by_env = [&](auto next) {
+        if constexpr (ENV_KERNEL) with_flag(S.env.kind != kEnvNone, next);
+        else next(std::false_type{});
+    };
+    if (N.shade) by_env([&](auto env) { by_bsdfs(env, std::true_type{}, N); });
+    else by_env([&](auto env) { with_flag(S.has_mesh, [&](auto mesh) { by_bsdfs(env, mesh); }); });
+}
 
 hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, const NormalsDev& N, int64_t path0, int spp,
                             uint64_t seed, hipStream_t st) {
-    if (N.shade) {
-        auto nrm = S.env.kind != kEnvNone ? li_camera_kernel<true, true, NormalsDev> : li_camera_kernel<true, false, NormalsDev>;
-        hipLaunchKernelGGL(nrm, grid_for(P.P), dim3(256), 0, st, S, P, path0, spp, seed, N);
-        return hipGetLastError();
-    }
-    auto kernel = S.env.kind != kEnvNone ? (S.has_mesh ? li_camera_kernel<true, true> : li_camera_kernel<false, true>)
-                                         : (S.has_mesh ? li_camera_kernel<true, false> : li_camera_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, grid_for(P.P), dim3(256), 0, st, S, P, path0, spp, seed);
+    li_variant<true>(S, N, [&](auto, auto, auto mesh, auto env, auto... nrm) {
+        hipLaunchKernelGGL((li_camera_kernel<mesh.value, env.value, decltype(nrm)...>), grid_for(P.P), dim3(256), 0, st,
+                           S, P, path0, spp, seed, nrm...);
+    });
     return hipGetLastError();
 }
 hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N, int64_t path0,
                            int bounce, int max_depth, int guided, float h, uint64_t seed, hipStream_t st) {
-    if (N.shade)
-        hipLaunchKernelGGL(LI_VARIANT_N(li_query_kernel, S), grid_for(P.P), dim3(256), 0, st, S, P, Q, path0,
-                           bounce, max_depth, guided, h, seed, N);
-    else
-        hipLaunchKernelGGL(LI_VARIANT(li_query_kernel, S), grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce,
-                           max_depth, guided, h, seed);
+    li_variant<false>(S, N, [&](auto phong, auto diel, auto mesh, auto, auto... nrm) {
+        hipLaunchKernelGGL((li_query_kernel<phong.value, diel.value, mesh.value, decltype(nrm)...>), grid_for(P.P),
+                           dim3(256), 0, st, S, P, Q, path0, bounce, max_depth, guided, h, seed, nrm...);
+    });
     return hipGetLastError();
 }
 size_t li_select_temp_bytes(int64_t n) {
@@ -1054,26 +1054,19 @@ hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDe
     hipError_t e = hipcub::DeviceSelect::Flagged(temp, temp_bytes, hipcub::CountingInputIterator<int32_t>(0), Q.live,
                                                  Q.idx, count_dev, (int)n, st);
     if (e != hipSuccess) return e;
-    if (N.shade)
-        hipLaunchKernelGGL(LI_VARIANT_N(li_compact_kernel, S), grid_for(n), dim3(256), 0, st, S, P, Q,
-                           (const int32_t*)count_dev, product, N);
-    else
-        hipLaunchKernelGGL(LI_VARIANT(li_compact_kernel, S), grid_for(n), dim3(256), 0, st, S, P, Q,
-                           (const int32_t*)count_dev, product);
+    li_variant<false>(S, N, [&](auto phong, auto diel, auto mesh, auto, auto... nrm) {
+        hipLaunchKernelGGL((li_compact_kernel<phong.value, diel.value, mesh.value, decltype(nrm)...>), grid_for(n),
+                           dim3(256), 0, st, S, P, Q, (const int32_t*)count_dev, product, nrm...);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N, int64_t path0,
                            int bounce, int rr_depth, float h, uint64_t seed, int product, hipStream_t st) {
-    if (N.shade) {
-        auto nrm = S.env.kind != kEnvNone ? LI_VARIANT_NE(li_shade_kernel, S, true)
-                                          : LI_VARIANT_NE(li_shade_kernel, S, false);
-        hipLaunchKernelGGL(nrm, grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce, rr_depth, h, seed, product,
-                           N);
-        return hipGetLastError();
-    }
-    auto kernel = S.env.kind != kEnvNone ? LI_VARIANT_E(li_shade_kernel, S, true) : LI_VARIANT_E(li_shade_kernel, S, false);
-    hipLaunchKernelGGL(kernel, grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce, rr_depth, h, seed, product);
+    li_variant<true>(S, N, [&](auto phong, auto diel, auto mesh, auto env, auto... nrm) {
+        hipLaunchKernelGGL((li_shade_kernel<phong.value, diel.value, mesh.value, env.value, decltype(nrm)...>),
+                           grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce, rr_depth, h, seed, product, nrm...);
+    });
     return hipGetLastError();
 }
 

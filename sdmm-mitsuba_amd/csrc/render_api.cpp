@@ -12,6 +12,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sdmm_gpu.h"
@@ -32,18 +33,7 @@ using namespace sdmm;
 struct sdmm_scene {
     int device = 0;
     SceneDev S{};
-    QuadDev* dquads = nullptr;
-    float* drefl = nullptr;
-    float* dbpar = nullptr;
-    float* dlmod = nullptr;   // kLearnedStride per BSDF (learned_models), null: none
-    float* dlmod_nd = nullptr;   // kLearnedNdStride per BSDF (learned_models_nd), null: none
-    int32_t* dtwosided = nullptr;   // 1 per two-sided BSDF (bsdf_twosided), null: no entry set
-    float* drad = nullptr;
-    BvhNode* dnodes = nullptr;   // the triangle mesh (mesh_bvh.h), null without one
-    MeshTri* dtris = nullptr;
-    MeshHit* dhits = nullptr;
-    MeshShade* dshade = nullptr;   // the mesh's vertex normals (shading_normal.h), null without them
-    EnvTexel* denv = nullptr;    // the lat-long environment map (envmap.h), null without one
+    std::vector<void*> owned;   // the device blocks behind S, N.shade and S.env.texels (upload), freed by destroy
     float smin[3] = {0, 0, 0}, snorm = 1.0f, tmin[3] = {0, 0, 0}, tmax[3] = {0, 0, 0};
     // per-render buffers (grown)
     void* buf = nullptr;
@@ -52,7 +42,7 @@ struct sdmm_scene {
     int cap_v = 0;
     PathsDev P{};
     QueryDev Q{};
-    NormalsDev N{};   // (vertex normals: N.shade = dshade, the ns / ng planes in buf)
+    NormalsDev N{};   // (vertex normals: N.shade the scene's, the ns / ng planes in buf)
     int64_t* dsum = nullptr;
     int32_t* dcount = nullptr;   // live guided queries of the current bounce
     int32_t* hcount = nullptr;   // (pinned host copy)
@@ -86,21 +76,68 @@ void cross3(const float a[3], const float b[3], float c[3]) {
 }
 float dot3h(const float a[3], const float b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
+constexpr size_t align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// The per-render arena of `cap` paths with `cv` vertex slots and `tb` bytes of
+// hipcub scratch: the path, query and vertex planes one after the other, each
+// on a 256-byte boundary.  base set: s->P, Q, N, dsum, temp and dcount point
+// into it; null: nothing is assigned.  Returns the arena's bytes either way.
+size_t layout_paths(sdmm_scene* s, char* base, int64_t cap, int cv, size_t tb) {
+    size_t off = 0;
+    auto take = [&](auto*& p, size_t bytes) {
+        if (base) p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off);
+        off += align256(bytes);
+    };
+    const size_t f = sizeof(float) * (size_t)cap, i4 = sizeof(int32_t) * (size_t)cap, u1 = (size_t)cap;
+    PathsDev& P = s->P;
+    QueryDev& Q = s->Q;
+    NormalsDev& N = s->N;
+    for (float** p : {&P.px, &P.py, &P.pz, &P.dx, &P.dy, &P.dz, &P.tr, &P.tg, &P.tb, &P.lr, &P.lg, &P.lb}) take(*p, f);
+    take(P.depth, i4);
+    take(P.quad, i4);
+    take(P.nv, i4);
+    take(P.nray, i4);
+    take(P.rec, sizeof(float) * (size_t)kVertexFields * (size_t)cv * (size_t)cap);
+    for (float** p : {&Q.c0, &Q.c1, &Q.c2, &Q.u0, &Q.u1, &Q.u2, &Q.b0, &Q.b1, &Q.b2, &Q.d0, &Q.d1, &Q.d2, &Q.pdf})
+        take(*p, f);
+    take(Q.mode, u1);
+    take(Q.comp, i4);
+    take(s->dsum, sizeof(int64_t));
+    take(s->temp, tb);
+    if (base) s->temp_bytes = align256(tb);
+    for (float** p : {&Q.k_c0, &Q.k_c1, &Q.k_c2, &Q.k_u0, &Q.k_u1, &Q.k_u2, &Q.k_b0, &Q.k_b1, &Q.k_b2}) take(*p, f);
+    take(Q.k_mode, u1);
+    take(Q.live, u1);
+    take(Q.idx, i4);
+    take(Q.slot, i4);
+    take(s->dcount, i4);
+    take(Q.ch, f);
+    take(Q.k_ch, f);
+    for (float*& p : Q.k_F) take(p, f);
+    take(Q.hq, f);
+    take(Q.k_mat, i4);
+    take(Q.bdelta, u1);
+    for (float** p : {&Q.bw0, &Q.bw1, &Q.bw2, &Q.bpdf}) take(*p, f);
+    // the eta planes: only with a dielectric or a kind-5 / 6 BSDF; the ns / ng
+    // planes: only with vertex normals (null otherwise, as created)
+    if (s->S.has_dielectric) {
+        take(P.eta, f);
+        take(Q.beta, f);
+    }
+    if (N.shade)
+        for (float** p : {&N.nsx, &N.nsy, &N.nsz, &N.ngx, &N.ngy, &N.ngz}) take(*p, f);
+    return off;
+}
+
 // path + query + vertex planes for P paths with V vertex slots
 int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
     if (P <= s->cap_paths && V <= s->cap_v && s->buf) return SDMM_OK;
-    const bool diel = s->S.has_dielectric != 0;   // (the eta planes: only with a dielectric or a kind-5 / 6 BSDF)
-    const bool nrm = s->N.shade != nullptr;       // (the ns / ng planes: only with vertex normals)
     const int64_t cap = std::max<int64_t>(P, s->cap_paths);
     const int cv = std::max(V, s->cap_v);
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t f = al(sizeof(float) * (size_t)cap), i4 = al(sizeof(int32_t) * (size_t)cap), u1 = al((size_t)cap);
-    const size_t recb = al(sizeof(float) * (size_t)kVertexFields * (size_t)cv * (size_t)cap);
     size_t tb = 0;
     (void)hipcub::DeviceReduce::Sum(nullptr, tb, (const int32_t*)nullptr, (int64_t*)nullptr, (int)cap);
     tb = std::max(tb, li_select_temp_bytes(cap));
-    const size_t need = 12 * f + 4 * i4 + recb + 13 * f + u1 + i4 + 256 + al(tb) + 9 * f + 2 * u1 + 3 * i4 +
-                        (1 + 1 + 9 + 1) * f + i4 + u1 + 4 * f + (diel ? 2 * f : 0) + (nrm ? 6 * f : 0);
+    const size_t need = layout_paths(s, nullptr, cap, cv, tb);
     HIP_TRY(hipStreamSynchronize(st));
     if (s->buf) HIP_TRY(hipFree(s->buf));
     s->buf = nullptr;
@@ -108,45 +145,28 @@ int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
     s->buf_bytes = need;
     s->cap_paths = cap;
     s->cap_v = cv;
-    char* b = (char*)s->buf;
-    auto take = [&](size_t n) { char* r = b; b += n; return r; };
-    float** pf[12] = {&s->P.px, &s->P.py, &s->P.pz, &s->P.dx, &s->P.dy, &s->P.dz,
-                      &s->P.tr, &s->P.tg, &s->P.tb, &s->P.lr, &s->P.lg, &s->P.lb};
-    for (float** q : pf) *q = (float*)take(f);
-    s->P.depth = (int*)take(i4);
-    s->P.quad = (int*)take(i4);
-    s->P.nv = (int*)take(i4);
-    s->P.nray = (int*)take(i4);
-    s->P.rec = (float*)take(recb);
-    float** qf[13] = {&s->Q.c0, &s->Q.c1, &s->Q.c2, &s->Q.u0, &s->Q.u1, &s->Q.u2, &s->Q.b0,
-                      &s->Q.b1, &s->Q.b2, &s->Q.d0, &s->Q.d1, &s->Q.d2, &s->Q.pdf};
-    for (float** q : qf) *q = (float*)take(f);
-    s->Q.mode = (uint8_t*)take(u1);
-    s->Q.comp = (int32_t*)take(i4);
-    s->dsum = (int64_t*)take(256);
-    s->temp = take(al(tb));
-    s->temp_bytes = al(tb);
-    float** kf[9] = {&s->Q.k_c0, &s->Q.k_c1, &s->Q.k_c2, &s->Q.k_u0, &s->Q.k_u1, &s->Q.k_u2,
-                     &s->Q.k_b0, &s->Q.k_b1, &s->Q.k_b2};
-    for (float** q : kf) *q = (float*)take(f);
-    s->Q.k_mode = (uint8_t*)take(u1);
-    s->Q.live = (uint8_t*)take(u1);
-    s->Q.idx = (int32_t*)take(i4);
-    s->Q.slot = (int32_t*)take(i4);
-    s->dcount = (int32_t*)take(i4);
-    s->Q.ch = (float*)take(f);
-    s->Q.k_ch = (float*)take(f);
-    for (int i = 0; i < 9; ++i) s->Q.k_F[i] = (float*)take(f);
-    s->Q.hq = (float*)take(f);
-    s->Q.k_mat = (int32_t*)take(i4);
-    s->Q.bdelta = (uint8_t*)take(u1);
-    float** bf[4] = {&s->Q.bw0, &s->Q.bw1, &s->Q.bw2, &s->Q.bpdf};
-    for (float** q : bf) *q = (float*)take(f);
-    s->P.eta = diel ? (float*)take(f) : nullptr;
-    s->Q.beta = diel ? (float*)take(f) : nullptr;
-    float** nf[6] = {&s->N.nsx, &s->N.nsy, &s->N.nsz, &s->N.ngx, &s->N.ngy, &s->N.ngz};
-    for (float** q : nf) *q = nrm ? (float*)take(f) : nullptr;
+    layout_paths(s, (char*)s->buf, cap, cv, tb);
     return SDMM_OK;
+}
+
+// the four blocks of an extended learned-BSDF table of `rows` rows of lM
+// lobes (weights, means, covariances, diffuse flags), laid out like the arena
+struct LearnedBlocks {
+    float *w, *m, *c;
+    uint8_t* dflag;
+};
+size_t layout_learned(LearnedBlocks* L, char* base, int64_t rows, int lM) {
+    size_t off = 0;
+    auto take = [&](auto*& p, size_t bytes) {
+        if (base) p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off);
+        off += bytes;
+    };
+    const size_t wb = align256(sizeof(float) * (size_t)rows * lM);
+    take(L->w, wb);
+    take(L->m, 3 * wb);
+    take(L->c, 4 * wb);
+    take(L->dflag, align256((size_t)rows));
+    return off;
 }
 
 // The extended learned-BSDF table of a render with rough conductors or Phong
@@ -159,9 +179,8 @@ int grow(sdmm_scene* s, int64_t P, int V, hipStream_t st) {
 int extend_learned(sdmm_scene* s, const sdmm_bsdf_table& user, int64_t cap, hipStream_t st, sdmm_bsdf_table* tab) {
     const int M = user.M, lM = std::max(M, kLearnedKeep), B = user.B;
     const int64_t rows = (int64_t)B + cap;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t wb = al(sizeof(float) * (size_t)rows * lM), mb = 3 * wb, cb = 4 * wb, db = al((size_t)rows);
-    const size_t need = wb + mb + cb + db;
+    LearnedBlocks L{};
+    const size_t need = layout_learned(&L, nullptr, rows, lM);
     if (need > s->lt_bytes) {
         HIP_TRY(hipStreamSynchronize(st));
         if (s->lt) HIP_TRY(hipFree(s->lt));
@@ -170,26 +189,22 @@ int extend_learned(sdmm_scene* s, const sdmm_bsdf_table& user, int64_t cap, hipS
         HIP_TRY(hipMalloc(&s->lt, need));
         s->lt_bytes = need;
     }
-    char* b = (char*)s->lt;
-    float* w = (float*)b;
-    float* m = (float*)(b + wb);
-    float* c = (float*)(b + wb + mb);
-    uint8_t* dflag = (uint8_t*)(b + wb + mb + cb);
-    HIP_TRY(hipMemsetAsync(w, 0, sizeof(float) * (size_t)B * lM, st));
-    HIP_TRY(hipMemcpy2DAsync(w, sizeof(float) * lM, user.weights, sizeof(float) * M, sizeof(float) * M, B,
+    layout_learned(&L, (char*)s->lt, rows, lM);
+    HIP_TRY(hipMemsetAsync(L.w, 0, sizeof(float) * (size_t)B * lM, st));
+    HIP_TRY(hipMemcpy2DAsync(L.w, sizeof(float) * lM, user.weights, sizeof(float) * M, sizeof(float) * M, B,
                              hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemsetAsync(m, 0, sizeof(float) * 3 * (size_t)B * lM, st));
-    HIP_TRY(hipMemcpy2DAsync(m, sizeof(float) * 3 * lM, user.means, sizeof(float) * 3 * M, sizeof(float) * 3 * M, B,
+    HIP_TRY(hipMemsetAsync(L.m, 0, sizeof(float) * 3 * (size_t)B * lM, st));
+    HIP_TRY(hipMemcpy2DAsync(L.m, sizeof(float) * 3 * lM, user.means, sizeof(float) * 3 * M, sizeof(float) * 3 * M, B,
                              hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemsetAsync(c, 0, sizeof(float) * 4 * (size_t)B * lM, st));
-    HIP_TRY(hipMemcpy2DAsync(c, sizeof(float) * 4 * lM, user.covs, sizeof(float) * 4 * M, sizeof(float) * 4 * M, B,
+    HIP_TRY(hipMemsetAsync(L.c, 0, sizeof(float) * 4 * (size_t)B * lM, st));
+    HIP_TRY(hipMemcpy2DAsync(L.c, sizeof(float) * 4 * lM, user.covs, sizeof(float) * 4 * M, sizeof(float) * 4 * M, B,
                              hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemsetAsync(dflag, 0, (size_t)rows, st));
-    if (user.diffuse) HIP_TRY(hipMemcpyAsync(dflag, user.diffuse, (size_t)B, hipMemcpyDeviceToDevice, st));
-    *tab = sdmm_bsdf_table{w, m, c, (int)std::min<int64_t>(rows, INT32_MAX), lM, dflag};
-    s->Q.lw = w;
-    s->Q.lm = m;
-    s->Q.lc = c;
+    HIP_TRY(hipMemsetAsync(L.dflag, 0, (size_t)rows, st));
+    if (user.diffuse) HIP_TRY(hipMemcpyAsync(L.dflag, user.diffuse, (size_t)B, hipMemcpyDeviceToDevice, st));
+    *tab = sdmm_bsdf_table{L.w, L.m, L.c, (int)std::min<int64_t>(rows, INT32_MAX), lM, L.dflag};
+    s->Q.lw = L.w;
+    s->Q.lm = L.m;
+    s->Q.lc = L.c;
     s->Q.lrow0 = B;
     s->Q.lM = lM;
     return SDMM_OK;
@@ -204,6 +219,93 @@ bool geometry_args_ok(const sdmm_scene_desc* d) {
 // some primitive may carry an emitter index (quads' or triangles' array set):
 // the radiance table is needed, uploaded and read then
 bool has_emitters(const sdmm_scene_desc* d) { return d->emitter || (d->n_triangles > 0 && d->tri_emitter); }
+int check_emitters(const sdmm_scene_desc* d, const char* who) {
+    if (has_emitters(d) && (d->n_emitters < 1 || !d->radiance))
+        return fail(SDMM_E_INVALID, std::string(who) + ": emitters without radiance");
+    return SDMM_OK;
+}
+
+// BSDF b's kind (render_device.h); without bsdf_params every BSDF is diffuse
+float bsdf_kind(const sdmm_scene_desc* d, int b) {
+    return d->bsdf_params ? d->bsdf_params[kBsdfParams * b] : (float)kBsdfDiffuse;
+}
+// a color triple: no negative channel, a finite sum
+bool rgb_ok(const float* c) {
+    return c[0] >= 0.0f && c[1] >= 0.0f && c[2] >= 0.0f && std::isfinite(c[0] + c[1] + c[2]);
+}
+// a bsdf_params row's specular reflectance (slots 1 .. 3)
+bool spec_ok(const float* bp) { return rgb_ok(bp + 1); }
+// one BSDF's bsdf_params row (render_device.h): its kind one of 0 .. 6, that
+// kind's slots in range (the plastic kind tests no finiteness)
+bool bsdf_params_ok(const float* bp) {
+    const auto fin = [](float x) { return std::isfinite(x); };
+    // eta = intIOR / extIOR of a dielectric and its inverse
+    const auto eta_ok = [&] { return bp[4] > 0.0f && bp[4] != 1.0f && fin(bp[4]) && bp[5] > 0.0f && fin(bp[5]); };
+    // a conductor's gray eta and k
+    const auto eta_k_ok = [&] { return bp[4] > 0.0f && fin(bp[4]) && bp[5] >= 0.0f && fin(bp[5]); };
+    const auto alpha_ok = [&] { return bp[6] > 0.0f && bp[6] <= 2.0f; };
+    int kind = -1;
+    for (int k = kBsdfDiffuse; k <= kBsdfSmoothConductor; ++k)
+        if (bp[0] == (float)k) kind = k;
+    switch (kind) {
+        case kBsdfDiffuse: return true;
+        case kBsdfPlastic: return bp[4] > 0.0f && bp[5] > 0.0f && bp[6] < 1.0f && bp[7] >= 0.0f && bp[7] <= 1.0f;
+        case kBsdfConductor: return spec_ok(bp) && eta_k_ok() && alpha_ok();
+        case kBsdfPhong: return spec_ok(bp) && bp[4] >= 0.0f && fin(bp[4]) && bp[5] >= 0.0f && bp[5] <= 1.0f;
+        case kBsdfDielectric: return spec_ok(bp) && eta_ok() && alpha_ok();
+        case kBsdfSmoothDielectric: return spec_ok(bp) && eta_ok();
+        case kBsdfSmoothConductor: return spec_ok(bp) && eta_k_ok();
+        default: return false;
+    }
+}
+// the kinds that condition a learned model per bounce (per-query lobes)
+bool per_query_kind(float kind) {
+    return kind == (float)kBsdfConductor || kind == (float)kBsdfPhong || kind == (float)kBsdfDielectric;
+}
+
+// the model's records (kLearnedRec / learned_rec(C) floats each) from the ABI
+// arrays; false: not a model (C, M or a missing array)
+bool pack_records(int C, int M, const float* weights, const float* means, const float* covs, float* rec) {
+    if ((C != 2 && C != 3) || M < 0 || M > kLearnedMaxComp || (M > 0 && (!weights || !means || !covs))) return false;
+    const int R = learned_rec(C), nm = C + 3, nc = (C + 2) * (C + 2);
+    for (int k = 0; k < M; ++k) {
+        float* r = rec + R * k;
+        r[0] = weights[k];
+        for (int i = 0; i < nm; ++i) r[1 + i] = means[nm * k + i];
+        for (int i = 0; i < nc; ++i) r[1 + nm + i] = covs[nc * k + i];
+    }
+    return true;
+}
+static_assert(learned_rec(2) == kLearnedRec, "an SDMM4 record is the C = 2 record");
+bool pack_learned4(const sdmm_learned_bsdf4* m, float* rec) {
+    return m && pack_records(2, m->M, m->weights, m->means, m->covs, rec);
+}
+bool pack_learned(const sdmm_learned_bsdf* m, float* rec) {
+    return m && pack_records(m->C, m->M, m->weights, m->means, m->covs, rec);
+}
+// M packed records over a C-dimensional condition: every value finite, no
+// negative weight, the mean's direction (after the condition) a unit vector
+bool learned_records_ok(const float* rec, int C, int M) {
+    const int R = learned_rec(C);
+    for (int k = 0; k < M; ++k) {
+        const float *r = rec + R * k, *dir = r + 1 + C;
+        bool ok = r[0] >= 0.0f;
+        for (int i = 0; i < R; ++i) ok = ok && std::isfinite(r[i]);
+        const double n2 = (double)dir[0] * dir[0] + (double)dir[1] * dir[1] + (double)dir[2] * dir[2];
+        if (!ok || std::fabs(n2 - 1.0) > 1e-5) return false;
+    }
+    return true;
+}
+
+// the device's float environment on this thread while in scope: denormals
+// flushed (-fgpu-flush-denormals-to-zero)
+struct DeviceFloatEnv {
+    const unsigned csr = _mm_getcsr();
+    DeviceFloatEnv() { _mm_setcsr(csr | 0x8040u); }
+    ~DeviceFloatEnv() { _mm_setcsr(csr); }
+    DeviceFloatEnv(const DeviceFloatEnv&) = delete;
+    DeviceFloatEnv& operator=(const DeviceFloatEnv&) = delete;
+};
 
 // the description's environment emitter, validated; *E gets every field but
 // the texel pointer.  0, or the error code (message set).
@@ -241,62 +343,21 @@ int prep_env(const sdmm_scene_desc* d, const char* who, EnvDev* E) {
     return SDMM_OK;
 }
 
-// the description's two-sided flags, validated (after geometry_args_ok); *any
-// (nullable): some entry is set.  0, or the error code (message set).
+// the description's two-sided flags, validated (after geometry_args_ok); *any:
+// some entry is set.  0, or the error code (message set).
 int prep_twosided(const sdmm_scene_desc* d, const char* who, bool* any) {
     const std::string w(who);
-    if (any) *any = false;
+    *any = false;
     if (!d->bsdf_twosided) return SDMM_OK;
     for (int b = 0; b < d->n_bsdfs; ++b) {
         const int32_t v = d->bsdf_twosided[b];
         if (v != 0 && v != 1) return fail(SDMM_E_INVALID, w + ": a bsdf_twosided entry other than 0 or 1");
         if (v == 0) continue;
         // "Only materials without a transmission component can be nested" (twosided.cpp:106-108)
-        const float kind = d->bsdf_params ? d->bsdf_params[kBsdfParams * b] : (float)kBsdfDiffuse;
+        const float kind = bsdf_kind(d, b);
         if (kind == (float)kBsdfDielectric || kind == (float)kBsdfSmoothDielectric)
             return fail(SDMM_E_INVALID, w + ": bsdf_twosided on a transmitting BSDF (kind 4 or 5)");
-        if (any) *any = true;
-    }
-    return SDMM_OK;
-}
-
-// the quads' derived data (normal, duals) and their corners' AABB, after the
-// description's argument checks.  0, or the error code (message set).
-int prep_quads(const sdmm_scene_desc* d, const char* who, std::vector<QuadDev>* qs, float mn[3], float mx[3]) {
-    const std::string w(who);
-    if (!geometry_args_ok(d)) return fail(SDMM_E_INVALID, w + ": invalid description");
-    if (d->mesh_normals && d->n_triangles < 1) return fail(SDMM_E_INVALID, w + ": mesh_normals without triangles");
-    if (const int rc = prep_twosided(d, who, nullptr)) return rc;
-    if (has_emitters(d) && (d->n_emitters < 1 || !d->radiance))
-        return fail(SDMM_E_INVALID, w + ": emitters without radiance");
-    qs->assign((size_t)d->n_quads, QuadDev{});
-    for (int q = 0; q < d->n_quads; ++q) {
-        QuadDev& Q = (*qs)[(size_t)q];
-        const float* v = d->quads + 9 * q;
-        for (int a = 0; a < 3; ++a) { Q.p0[a] = v[a]; Q.e1[a] = v[3 + a]; Q.e2[a] = v[6 + a]; }
-        float n[3];
-        cross3(Q.e1, Q.e2, n);
-        const float len = std::sqrt(dot3h(n, n));
-        if (!(len > 0.0f)) return fail(SDMM_E_INVALID, w + ": degenerate quad");
-        const float sg = (d->flip_normals && d->flip_normals[q]) ? -1.0f : 1.0f;
-        for (int a = 0; a < 3; ++a) Q.n[a] = sg * n[a] / len;
-        // duals: g1 . e1 = 1, g1 . e2 = 0 (g1 ~ e2 x n), likewise g2
-        float a1[3], a2[3];
-        cross3(Q.e2, n, a1);
-        cross3(n, Q.e1, a2);
-        const float s1 = dot3h(Q.e1, a1), s2 = dot3h(Q.e2, a2);
-        for (int a = 0; a < 3; ++a) { Q.g1[a] = a1[a] / s1; Q.g2[a] = a2[a] / s2; }
-        Q.bsdf = d->bsdf[q];
-        Q.emitter = d->emitter ? d->emitter[q] : -1;
-        if (Q.bsdf < 0 || Q.bsdf >= d->n_bsdfs || Q.emitter < -1 || (Q.emitter >= 0 && Q.emitter >= d->n_emitters))
-            return fail(SDMM_E_INVALID, w + ": material index out of range");
-        // scene AABB without the camera: the four corners
-        for (int c = 0; c < 4; ++c)
-            for (int a = 0; a < 3; ++a) {
-                const float x = Q.p0[a] + ((c & 1) ? Q.e1[a] : 0.0f) + ((c & 2) ? Q.e2[a] : 0.0f);
-                mn[a] = std::min(mn[a], x);
-                mx[a] = std::max(mx[a], x);
-            }
+        *any = true;
     }
     return SDMM_OK;
 }
@@ -320,71 +381,125 @@ int prep_mesh(const sdmm_scene_desc* d, const char* who, int max_levels, MeshBvh
     return SDMM_OK;
 }
 
+// A description's geometry on the host, as sdmm_scene_create uploads it and
+// the *_host entries read it: the quads' derived data (normal, duals), the
+// mesh with its BVH (has_mesh), the AABB of the quads' corners and the mesh's
+// vertices (without the camera), and whether some BSDF is two-sided.
+struct HostScene {
+    std::vector<QuadDev> quads;
+    MeshBvh mesh;
+    bool has_mesh = false, twosided = false;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+};
+
+// validates the description's geometry and material arguments and builds
+// *hs.  0, or the error code (message set).
+int build_host_scene(const sdmm_scene_desc* d, const char* who, int max_levels, HostScene* hs) {
+    const std::string w(who);
+    if (!geometry_args_ok(d)) return fail(SDMM_E_INVALID, w + ": invalid description");
+    if (d->mesh_normals && d->n_triangles < 1) return fail(SDMM_E_INVALID, w + ": mesh_normals without triangles");
+    if (const int rc = prep_twosided(d, who, &hs->twosided)) return rc;
+    if (const int rc = check_emitters(d, who)) return rc;
+    hs->quads.assign((size_t)d->n_quads, QuadDev{});
+    for (int q = 0; q < d->n_quads; ++q) {
+        QuadDev& Q = hs->quads[(size_t)q];
+        const float* v = d->quads + 9 * q;
+        for (int a = 0; a < 3; ++a) { Q.p0[a] = v[a]; Q.e1[a] = v[3 + a]; Q.e2[a] = v[6 + a]; }
+        float n[3];
+        cross3(Q.e1, Q.e2, n);
+        const float len = std::sqrt(dot3h(n, n));
+        if (!(len > 0.0f)) return fail(SDMM_E_INVALID, w + ": degenerate quad");
+        const float sg = (d->flip_normals && d->flip_normals[q]) ? -1.0f : 1.0f;
+        for (int a = 0; a < 3; ++a) Q.n[a] = sg * n[a] / len;
+        // duals: g1 . e1 = 1, g1 . e2 = 0 (g1 ~ e2 x n), likewise g2
+        float a1[3], a2[3];
+        cross3(Q.e2, n, a1);
+        cross3(n, Q.e1, a2);
+        const float s1 = dot3h(Q.e1, a1), s2 = dot3h(Q.e2, a2);
+        for (int a = 0; a < 3; ++a) { Q.g1[a] = a1[a] / s1; Q.g2[a] = a2[a] / s2; }
+        Q.bsdf = d->bsdf[q];
+        Q.emitter = d->emitter ? d->emitter[q] : -1;
+        if (Q.bsdf < 0 || Q.bsdf >= d->n_bsdfs || Q.emitter < -1 || (Q.emitter >= 0 && Q.emitter >= d->n_emitters))
+            return fail(SDMM_E_INVALID, w + ": material index out of range");
+        for (int c = 0; c < 4; ++c)
+            for (int a = 0; a < 3; ++a) {
+                const float x = Q.p0[a] + ((c & 1) ? Q.e1[a] : 0.0f) + ((c & 2) ? Q.e2[a] : 0.0f);
+                hs->mn[a] = std::min(hs->mn[a], x);
+                hs->mx[a] = std::max(hs->mx[a], x);
+            }
+    }
+    hs->has_mesh = d->n_triangles > 0;
+    if (hs->has_mesh) {
+        if (const int rc = prep_mesh(d, who, max_levels, &hs->mesh)) return rc;
+        for (int a = 0; a < 3; ++a) {
+            hs->mn[a] = std::min(hs->mn[a], hs->mesh.mn[a]);
+            hs->mx[a] = std::max(hs->mx[a], hs->mesh.mx[a]);
+        }
+    }
+    return SDMM_OK;
+}
+
+// the closest hit of the ray (o, d) with t in (mint, maxt) among the quads and
+// the triangles (mode 0: the BVH, 1: the loop over all of them): the
+// primitive or -1, *t its distance (maxt without one)
+int closest(const HostScene& hs, int mode, const float o[3], const float d[3], float mint, float maxt, float* t) {
+    const int nquads = (int)hs.quads.size();
+    int best = quads_closest(hs.quads.data(), nquads, o, d, mint, maxt, *t);
+    if (hs.has_mesh) mesh_closest_host(hs.mesh, nquads, mode, o, d, mint, maxt, best, *t);
+    return best;
+}
+
+// n elements of host memory as a device block of max(n, alloc) elements that
+// sdmm_scene_destroy frees; *out: the block.  Nothing to hold: *out stays.
+template <class T>
+hipError_t upload(sdmm_scene* s, const T* host, size_t n, const T** out, size_t alloc = 0) {
+    alloc = std::max(n, alloc);
+    if (alloc == 0) return hipSuccess;
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, sizeof(T) * alloc);
+    if (e != hipSuccess) return e;
+    s->owned.push_back(p);
+    *out = static_cast<const T*>(p);
+    return n ? hipMemcpy(p, host, sizeof(T) * n, hipMemcpyHostToDevice) : hipSuccess;
+}
+
 }  // namespace
 
 extern "C" {
 
 int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
+    const char* who = "sdmm_scene_create";
+    const std::string w(who);
     if (!out || !d || !geometry_args_ok(d) || d->width < 1 || d->height < 1 ||
         !(d->fov_x_deg > 0.0f && d->fov_x_deg < 180.0f))
-        return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid description");
-    if (has_emitters(d) && (d->n_emitters < 1 || !d->radiance))
-        return fail(SDMM_E_INVALID, "sdmm_scene_create: emitters without radiance");
+        return fail(SDMM_E_INVALID, w + ": invalid description");
+    if (const int rc = check_emitters(d, who)) return rc;
     if (d->bsdf_params)
         for (int b = 0; b < d->n_bsdfs; ++b) {
-            const float* bp = d->bsdf_params + kBsdfParams * b;
-            const bool ok = bp[0] == (float)kBsdfDiffuse ||
-                            (bp[0] == (float)kBsdfPlastic && bp[4] > 0.0f && bp[5] > 0.0f && bp[6] < 1.0f &&
-                             bp[7] >= 0.0f && bp[7] <= 1.0f) ||
-                            (bp[0] == (float)kBsdfConductor && bp[1] >= 0.0f && bp[2] >= 0.0f && bp[3] >= 0.0f &&
-                             std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] > 0.0f && std::isfinite(bp[4]) &&
-                             bp[5] >= 0.0f && std::isfinite(bp[5]) && bp[6] > 0.0f && bp[6] <= 2.0f) ||
-                            (bp[0] == (float)kBsdfPhong && bp[1] >= 0.0f && bp[2] >= 0.0f && bp[3] >= 0.0f &&
-                             std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] >= 0.0f && std::isfinite(bp[4]) &&
-                             bp[5] >= 0.0f && bp[5] <= 1.0f) ||
-                            (bp[0] == (float)kBsdfDielectric && bp[1] >= 0.0f && bp[2] >= 0.0f && bp[3] >= 0.0f &&
-                             std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] > 0.0f && bp[4] != 1.0f &&
-                             std::isfinite(bp[4]) && bp[5] > 0.0f && std::isfinite(bp[5]) && bp[6] > 0.0f &&
-                             bp[6] <= 2.0f) ||
-                            (bp[0] == (float)kBsdfSmoothDielectric && bp[1] >= 0.0f && bp[2] >= 0.0f &&
-                             bp[3] >= 0.0f && std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] > 0.0f &&
-                             bp[4] != 1.0f && std::isfinite(bp[4]) && bp[5] > 0.0f && std::isfinite(bp[5])) ||
-                            (bp[0] == (float)kBsdfSmoothConductor && bp[1] >= 0.0f && bp[2] >= 0.0f &&
-                             bp[3] >= 0.0f && std::isfinite(bp[1] + bp[2] + bp[3]) && bp[4] > 0.0f &&
-                             std::isfinite(bp[4]) && bp[5] >= 0.0f && std::isfinite(bp[5]));
-            if (!ok) return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid bsdf_params");
+            if (!bsdf_params_ok(d->bsdf_params + kBsdfParams * b))
+                return fail(SDMM_E_INVALID, w + ": invalid bsdf_params");
             // a smooth dielectric's specularTransmittance (its reflectance row)
-            const float* tr = d->reflectance + 3 * b;
-            if (bp[0] == (float)kBsdfSmoothDielectric &&
-                !(tr[0] >= 0.0f && tr[1] >= 0.0f && tr[2] >= 0.0f && std::isfinite(tr[0] + tr[1] + tr[2])))
-                return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid bsdf_params (a smooth dielectric's "
-                                            "transmittance is negative or not finite)");
+            if (bsdf_kind(d, b) == (float)kBsdfSmoothDielectric && !rgb_ok(d->reflectance + 3 * b))
+                return fail(SDMM_E_INVALID, w + ": invalid bsdf_params (a smooth dielectric's transmittance is "
+                                                "negative or not finite)");
         }
-    // learned models: at most kLearnedMaxComp components, finite, unit directions
+    // learned models: at most kLearnedMaxComp components, finite, unit
+    // directions.  M == 0: none; a delta-only BSDF never calls getDMM: its
+    // entry is not read, not even checked
+    const auto no_model = [&](int b, int M) { return M == 0 || is_smooth_kind(bsdf_kind(d, b)); };
+    const std::string bad_records =
+        w + ": learned model with a non-finite value, a negative weight or a non-unit direction";
     std::vector<float> lmod;
     if (d->learned_models) {
         lmod.assign((size_t)kLearnedStride * (size_t)d->n_bsdfs, 0.0f);
         for (int b = 0; b < d->n_bsdfs; ++b) {
             const sdmm_learned_bsdf4& L = d->learned_models[b];
-            if (L.M == 0) continue;
-            // (a delta-only BSDF never calls getDMM: its entry is not read, not even checked)
-            if (d->bsdf_params && is_smooth_kind(d->bsdf_params[kBsdfParams * b])) continue;
-            if (L.M < 0 || L.M > kLearnedMaxComp || !L.weights || !L.means || !L.covs)
-                return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid learned model (1 <= M <= 8, arrays)");
+            if (no_model(b, L.M)) continue;
             float* o = lmod.data() + (size_t)kLearnedStride * b;
+            if (!pack_learned4(&L, o + 1))
+                return fail(SDMM_E_INVALID, w + ": invalid learned model (1 <= M <= 8, arrays)");
             o[0] = (float)L.M;
-            for (int k = 0; k < L.M; ++k) {
-                float* r = o + 1 + kLearnedRec * k;
-                r[0] = L.weights[k];
-                for (int i = 0; i < 5; ++i) r[1 + i] = L.means[5 * k + i];
-                for (int i = 0; i < 16; ++i) r[6 + i] = L.covs[16 * k + i];
-                bool ok = r[0] >= 0.0f;
-                for (int i = 0; i < kLearnedRec; ++i) ok = ok && std::isfinite(r[i]);
-                const double n2 = (double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5];
-                if (!ok || std::fabs(n2 - 1.0) > 1e-5)
-                    return fail(SDMM_E_INVALID, "sdmm_scene_create: learned model with a non-finite value, a "
-                                                "negative weight or a non-unit direction");
-            }
+            if (!learned_records_ok(o + 1, 2, L.M)) return fail(SDMM_E_INVALID, bad_records);
         }
     }
     // learned models over a C-dimensional condition: the same checks; a Phong
@@ -395,56 +510,27 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
         lmod_nd.assign((size_t)kLearnedNdStride * (size_t)d->n_bsdfs, 0.0f);
         for (int b = 0; b < d->n_bsdfs; ++b) {
             const sdmm_learned_bsdf& L = d->learned_models_nd[b];
-            if (L.M == 0) continue;
-            if (d->bsdf_params && is_smooth_kind(d->bsdf_params[kBsdfParams * b])) continue;   // (as above)
-            if ((L.C != 2 && L.C != 3) || L.M < 0 || L.M > kLearnedMaxComp || !L.weights || !L.means || !L.covs)
-                return fail(SDMM_E_INVALID, "sdmm_scene_create: invalid learned model (C 2 or 3, 1 <= M <= 8, arrays)");
-            const bool phong = d->bsdf_params && d->bsdf_params[kBsdfParams * b] == (float)kBsdfPhong;
-            if (phong && (L.C != 3 || L.M <= kPhongDiffuseComponent))
-                return fail(SDMM_E_INVALID, "sdmm_scene_create: a Phong BSDF's learned model needs C = 3 and M >= 2");
-            const bool diel = d->bsdf_params && d->bsdf_params[kBsdfParams * b] == (float)kBsdfDielectric;
-            if (diel && L.C != 3)
-                return fail(SDMM_E_INVALID, "sdmm_scene_create: a rough dielectric's learned model needs C = 3");
-            const int R = learned_rec(L.C), nm = L.C + 3, nc = (L.C + 2) * (L.C + 2);
+            if (no_model(b, L.M)) continue;
             float* o = lmod_nd.data() + (size_t)kLearnedNdStride * b;
+            if (!pack_learned(&L, o + 2))
+                return fail(SDMM_E_INVALID, w + ": invalid learned model (C 2 or 3, 1 <= M <= 8, arrays)");
+            if (bsdf_kind(d, b) == (float)kBsdfPhong && (L.C != 3 || L.M <= kPhongDiffuseComponent))
+                return fail(SDMM_E_INVALID, w + ": a Phong BSDF's learned model needs C = 3 and M >= 2");
+            if (bsdf_kind(d, b) == (float)kBsdfDielectric && L.C != 3)
+                return fail(SDMM_E_INVALID, w + ": a rough dielectric's learned model needs C = 3");
             o[0] = (float)L.C;
             o[1] = (float)L.M;
-            for (int k = 0; k < L.M; ++k) {
-                float* r = o + 2 + R * k;
-                r[0] = L.weights[k];
-                for (int i = 0; i < nm; ++i) r[1 + i] = L.means[nm * k + i];
-                for (int i = 0; i < nc; ++i) r[1 + nm + i] = L.covs[nc * k + i];
-                bool ok = r[0] >= 0.0f;
-                for (int i = 0; i < R; ++i) ok = ok && std::isfinite(r[i]);
-                const float* dir = r + 1 + L.C;
-                const double n2 = (double)dir[0] * dir[0] + (double)dir[1] * dir[1] + (double)dir[2] * dir[2];
-                if (!ok || std::fabs(n2 - 1.0) > 1e-5)
-                    return fail(SDMM_E_INVALID, "sdmm_scene_create: learned model with a non-finite value, a "
-                                                "negative weight or a non-unit direction");
-            }
+            if (!learned_records_ok(o + 2, L.C, L.M)) return fail(SDMM_E_INVALID, bad_records);
         }
     }
     *out = nullptr;
-    std::vector<QuadDev> qs;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    int rc = prep_quads(d, "sdmm_scene_create", &qs, mn, mx);
+    // the quads' derived data, the triangle mesh with its BVH, their AABB
+    HostScene hs;
+    int rc = build_host_scene(d, who, 0, &hs);
     if (rc) return rc;
-    bool twosided = false;   // (validated in prep_quads; all zeros: no device table)
-    rc = prep_twosided(d, "sdmm_scene_create", &twosided);
-    if (rc) return rc;
-    // the triangle mesh: validated, its BVH built; the AABB takes its vertices in
-    MeshBvh mesh;
-    if (d->n_triangles > 0) {
-        rc = prep_mesh(d, "sdmm_scene_create", 0, &mesh);
-        if (rc) return rc;
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = std::min(mn[a], mesh.mn[a]);
-            mx[a] = std::max(mx[a], mesh.mx[a]);
-        }
-    }
     // the environment emitter: validated, a lat-long map as RGBA texels (envmap.h)
     EnvDev env;
-    rc = prep_env(d, "sdmm_scene_create", &env);
+    rc = prep_env(d, who, &env);
     if (rc) return rc;
     std::vector<EnvTexel> env_texels;
     if (env.kind == kEnvLatLong) {
@@ -455,84 +541,47 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     sdmm_scene* s = new (std::nothrow) sdmm_scene();
     if (!s) return fail(SDMM_E_NOMEM, "out of host memory");
     s->device = device;
-    // (a conductor some quad uses: the CPU restatement's rule)
-    if (d->bsdf_params)
-        for (int q = 0; q < d->n_quads; ++q)
-            if (d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfConductor ||
-                d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfPhong ||
-                d->bsdf_params[kBsdfParams * d->bsdf[q]] == (float)kBsdfDielectric)
-                s->per_query_lobes = true;
-    if (d->bsdf_params)
-        for (int i = 0; i < d->n_triangles; ++i) {
-            const float kind = d->bsdf_params[kBsdfParams * d->tri_bsdf[i]];
-            if (kind == (float)kBsdfConductor || kind == (float)kBsdfPhong || kind == (float)kBsdfDielectric)
-                s->per_query_lobes = true;
-        }
+    // (a conductor, Phong BSDF or rough dielectric some primitive uses: the CPU restatement's rule)
+    for (int q = 0; q < d->n_quads; ++q)
+        if (per_query_kind(bsdf_kind(d, d->bsdf[q]))) s->per_query_lobes = true;
+    for (int i = 0; i < d->n_triangles; ++i)
+        if (per_query_kind(bsdf_kind(d, d->tri_bsdf[i]))) s->per_query_lobes = true;
     // render() (volpath_sdmm.cpp:375-393): spatialNormalization = the largest
     // extent; the tree box getAABB (:314-332)
     float ext[3], norm = 0.0f;
-    for (int a = 0; a < 3; ++a) { ext[a] = mx[a] - mn[a]; norm = std::max(norm, ext[a]); }
+    for (int a = 0; a < 3; ++a) { ext[a] = hs.mx[a] - hs.mn[a]; norm = std::max(norm, ext[a]); }
     for (int a = 0; a < 3; ++a) {
-        s->smin[a] = mn[a];
+        s->smin[a] = hs.mn[a];
         s->tmin[a] = 0.0f - 1e-5f;
         s->tmax[a] = ext[a] / norm + 1e-5f;
     }
     s->snorm = norm;
+    // the device tables: an empty one (no mesh, no vertex normals, no map, no
+    // emitter, no bsdf_params, no model, no two-sided entry) stays null
+    SceneDev& S = s->S;
     hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipMalloc(&s->dquads, sizeof(QuadDev) * std::max<size_t>(qs.size(), 1));
-    if (e == hipSuccess && d->n_triangles > 0) e = hipMalloc(&s->dnodes, sizeof(BvhNode) * mesh.nodes.size());
-    if (e == hipSuccess && d->n_triangles > 0) e = hipMalloc(&s->dtris, sizeof(MeshTri) * mesh.tris.size());
-    if (e == hipSuccess && d->n_triangles > 0) e = hipMalloc(&s->dhits, sizeof(MeshHit) * mesh.hits.size());
-    if (e == hipSuccess && d->n_triangles > 0)
-        e = hipMemcpy(s->dnodes, mesh.nodes.data(), sizeof(BvhNode) * mesh.nodes.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && d->n_triangles > 0)
-        e = hipMemcpy(s->dtris, mesh.tris.data(), sizeof(MeshTri) * mesh.tris.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && d->n_triangles > 0)
-        e = hipMemcpy(s->dhits, mesh.hits.data(), sizeof(MeshHit) * mesh.hits.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !mesh.shade.empty()) e = hipMalloc(&s->dshade, sizeof(MeshShade) * mesh.shade.size());
-    if (e == hipSuccess && !mesh.shade.empty())
-        e = hipMemcpy(s->dshade, mesh.shade.data(), sizeof(MeshShade) * mesh.shade.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !env_texels.empty()) e = hipMalloc(&s->denv, sizeof(EnvTexel) * env_texels.size());
-    if (e == hipSuccess && !env_texels.empty())
-        e = hipMemcpy(s->denv, env_texels.data(), sizeof(EnvTexel) * env_texels.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&s->drefl, sizeof(float) * 3 * (size_t)d->n_bsdfs);
-    if (e == hipSuccess && has_emitters(d)) e = hipMalloc(&s->drad, sizeof(float) * 3 * (size_t)d->n_emitters);
-    if (e == hipSuccess && d->bsdf_params)
-        e = hipMalloc(&s->dbpar, sizeof(float) * kBsdfParams * (size_t)d->n_bsdfs);
-    if (e == hipSuccess && d->bsdf_params)
-        e = hipMemcpy(s->dbpar, d->bsdf_params, sizeof(float) * kBsdfParams * (size_t)d->n_bsdfs,
-                      hipMemcpyHostToDevice);
-    if (e == hipSuccess && !lmod.empty()) e = hipMalloc(&s->dlmod, sizeof(float) * lmod.size());
-    if (e == hipSuccess && !lmod.empty())
-        e = hipMemcpy(s->dlmod, lmod.data(), sizeof(float) * lmod.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !lmod_nd.empty()) e = hipMalloc(&s->dlmod_nd, sizeof(float) * lmod_nd.size());
-    if (e == hipSuccess && !lmod_nd.empty())
-        e = hipMemcpy(s->dlmod_nd, lmod_nd.data(), sizeof(float) * lmod_nd.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && twosided) e = hipMalloc(&s->dtwosided, sizeof(int32_t) * (size_t)d->n_bsdfs);
-    if (e == hipSuccess && twosided)
-        e = hipMemcpy(s->dtwosided, d->bsdf_twosided, sizeof(int32_t) * (size_t)d->n_bsdfs, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !qs.empty())
-        e = hipMemcpy(s->dquads, qs.data(), sizeof(QuadDev) * qs.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-        e = hipMemcpy(s->drefl, d->reflectance, sizeof(float) * 3 * (size_t)d->n_bsdfs, hipMemcpyHostToDevice);
-    if (e == hipSuccess && has_emitters(d))
-        e = hipMemcpy(s->drad, d->radiance, sizeof(float) * 3 * (size_t)d->n_emitters, hipMemcpyHostToDevice);
+    const auto up = [&](const auto* host, size_t n, auto out, size_t alloc = 0) {
+        if (e == hipSuccess) e = upload(s, host, n, out, alloc);
+    };
+    const size_t nb = (size_t)d->n_bsdfs;
+    const EnvTexel* texels = nullptr;
+    up(hs.quads.data(), hs.quads.size(), &S.quads, 1);
+    up(hs.mesh.nodes.data(), hs.mesh.nodes.size(), &S.nodes);
+    up(hs.mesh.tris.data(), hs.mesh.tris.size(), &S.tris);
+    up(hs.mesh.hits.data(), hs.mesh.hits.size(), &S.hits);
+    up(hs.mesh.shade.data(), hs.mesh.shade.size(), &s->N.shade);
+    up(env_texels.data(), env_texels.size(), &texels);
+    up(d->reflectance, 3 * nb, &S.refl);
+    up(d->radiance, has_emitters(d) ? 3 * (size_t)d->n_emitters : 0, &S.rad);
+    up(d->bsdf_params, d->bsdf_params ? kBsdfParams * nb : 0, &S.bpar);
+    up(lmod.data(), lmod.size(), &S.lmodel);
+    up(lmod_nd.data(), lmod_nd.size(), &S.lmodel_nd);
+    up(d->bsdf_twosided, hs.twosided ? nb : 0, &S.twosided);
     if (e != hipSuccess) {
         sdmm_scene_destroy(s);
-        return fail(SDMM_E_HIP, std::string("sdmm_scene_create: ") + hipGetErrorString(e));
+        return fail(SDMM_E_HIP, w + ": " + hipGetErrorString(e));
     }
-    SceneDev& S = s->S;
-    S.quads = s->dquads;
     S.n_quads = d->n_quads;
-    S.refl = s->drefl;
-    S.bpar = s->dbpar;
-    S.lmodel = s->dlmod;
-    S.lmodel_nd = s->dlmod_nd;
-    S.twosided = s->dtwosided;
-    S.nodes = s->dnodes;
-    S.tris = s->dtris;
-    S.hits = s->dhits;
-    s->N.shade = s->dshade;
     S.n_tris = d->n_triangles;
     S.has_mesh = d->n_triangles > 0 ? 1 : 0;
     {
@@ -547,9 +596,8 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
             // (the delta-only kinds live in the DIEL kernels: no variant of their own)
             if (is_smooth_kind(d->bsdf_params[kBsdfParams * b])) S.has_dielectric = 1;
         }
-    S.rad = s->drad;
     S.env = env;
-    S.env.texels = reinterpret_cast<const float*>(s->denv);
+    S.env.texels = reinterpret_cast<const float*>(texels);
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 4; ++c) S.cam[4 * r + c] = d->camera_to_world[4 * r + c];
     S.tanx = (float)std::tan(0.5 * (double)d->fov_x_deg * 3.14159265358979323846 / 180.0);
@@ -565,25 +613,18 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
 
 int sdmm_learned4_conditional(const sdmm_learned_bsdf4* m, float alpha, const float wi_local[3], int keep,
                               int* n_out, float* weights, float* means, float* covs) {
-    if (!m || !wi_local || !n_out || keep < 1 || m->M < 0 || m->M > kLearnedMaxComp ||
-        (m->M > 0 && (!m->weights || !m->means || !m->covs)) || !weights || !means || !covs)
+    float rec[kLearnedMaxComp * kLearnedRec];
+    if (!pack_learned4(m, rec) || !wi_local || !n_out || keep < 1 || !weights || !means || !covs)
         return fail(SDMM_E_INVALID, "sdmm_learned4_conditional: invalid argument");
     *n_out = 0;
     if (m->M == 0 || !(wi_local[2] > 0.0f)) return SDMM_OK;   // getDMM: no model, or cosTheta(wi) <= 0
-    float rec[kLearnedMaxComp * kLearnedRec];
-    for (int k = 0; k < m->M; ++k) {
-        float* r = rec + kLearnedRec * k;
-        r[0] = m->weights[k];
-        for (int i = 0; i < 5; ++i) r[1 + i] = m->means[5 * k + i];
-        for (int i = 0; i < 16; ++i) r[6 + i] = m->covs[16 * k + i];
-    }
-    // the device's float environment: denormals flushed (-fgpu-flush-denormals-to-zero)
-    const unsigned csr = _mm_getcsr();
-    _mm_setcsr(csr | 0x8040u);
-    const float theta = (float)std::acos((double)std::fmin(1.0f, wi_local[2]));
     float w[kLearnedMaxComp], mm[3 * kLearnedMaxComp], cc[4 * kLearnedMaxComp];
-    const int n = learned4_conditional(rec, m->M, theta, alpha, wi_local, keep, w, mm, cc);
-    _mm_setcsr(csr);
+    int n;
+    {
+        const DeviceFloatEnv env;
+        const float theta = (float)std::acos((double)std::fmin(1.0f, wi_local[2]));
+        n = learned4_conditional(rec, m->M, theta, alpha, wi_local, keep, w, mm, cc);
+    }
     for (int j = 0; j < n; ++j) {
         weights[j] = w[j];
         for (int i = 0; i < 3; ++i) means[3 * j + i] = mm[3 * j + i];
@@ -596,40 +637,16 @@ int sdmm_learned4_conditional(const sdmm_learned_bsdf4* m, float alpha, const fl
 int sdmm_learned4_conditional_device(const sdmm_learned_bsdf4* m, float alpha, int64_t nq, const float* const wi_local[3],
                                      int keep, float* weights, float* means, float* covs, int32_t* n_out,
                                      void* hip_stream) {
-    if (!m || nq < 0 || keep < 1 || keep > kLearnedMaxComp || m->M < 0 || m->M > kLearnedMaxComp ||
-        (m->M > 0 && (!m->weights || !m->means || !m->covs)))
+    float rec[kLearnedMaxComp * kLearnedRec];
+    if (!pack_learned4(m, rec) || nq < 0 || keep < 1 || keep > kLearnedMaxComp)
         return fail(SDMM_E_INVALID, "sdmm_learned4_conditional_device: invalid argument");
     if (nq == 0) return SDMM_OK;
     if (!wi_local || !wi_local[0] || !wi_local[1] || !wi_local[2] || !weights || !means || !covs || !n_out)
         return fail(SDMM_E_INVALID, "sdmm_learned4_conditional_device: invalid argument");
-    float rec[kLearnedMaxComp * kLearnedRec];
-    for (int k = 0; k < m->M; ++k) {
-        float* r = rec + kLearnedRec * k;
-        r[0] = m->weights[k];
-        for (int i = 0; i < 5; ++i) r[1 + i] = m->means[5 * k + i];
-        for (int i = 0; i < 16; ++i) r[6 + i] = m->covs[16 * k + i];
-    }
     HIP_TRY(launch_learned4(rec, m->M, alpha, nq, wi_local, keep, weights, means, covs, n_out,
                             (hipStream_t)hip_stream));
     return SDMM_OK;
 }
-
-namespace {
-// the model's records (learned_rec(C) floats each) from the ABI arrays
-bool pack_learned(const sdmm_learned_bsdf* m, float* rec) {
-    if (!m || (m->C != 2 && m->C != 3) || m->M < 0 || m->M > kLearnedMaxComp ||
-        (m->M > 0 && (!m->weights || !m->means || !m->covs)))
-        return false;
-    const int R = learned_rec(m->C), nm = m->C + 3, nc = (m->C + 2) * (m->C + 2);
-    for (int k = 0; k < m->M; ++k) {
-        float* r = rec + R * k;
-        r[0] = m->weights[k];
-        for (int i = 0; i < nm; ++i) r[1 + i] = m->means[nm * k + i];
-        for (int i = 0; i < nc; ++i) r[1 + nm + i] = m->covs[nc * k + i];
-    }
-    return true;
-}
-}  // namespace
 
 int sdmm_learned_conditional(const sdmm_learned_bsdf* m, const float* cond_rest, const float wi_local[3], int keep,
                              int force, int* n_out, float* weights, float* means, float* covs) {
@@ -640,16 +657,16 @@ int sdmm_learned_conditional(const sdmm_learned_bsdf* m, const float* cond_rest,
                                     "-1 <= force < M)");
     *n_out = 0;
     if (m->M == 0 || !(wi_local[2] > 0.0f)) return SDMM_OK;   // getDMM: no model, or cosTheta(wi) <= 0
-    // the device's float environment: denormals flushed (-fgpu-flush-denormals-to-zero)
-    const unsigned csr = _mm_getcsr();
-    _mm_setcsr(csr | 0x8040u);
-    float x[kLearnedMaxCond];
-    x[0] = (float)std::acos((double)std::fmin(1.0f, wi_local[2]));
-    for (int i = 0; i < m->C - 1; ++i) x[1 + i] = cond_rest[i];
     float w[kLearnedMaxComp], mm[3 * kLearnedMaxComp], cc[4 * kLearnedMaxComp];
-    const int n = m->C == 2 ? learned_conditional<2>(rec, m->M, x, wi_local, keep, force, w, mm, cc)
-                            : learned_conditional<3>(rec, m->M, x, wi_local, keep, force, w, mm, cc);
-    _mm_setcsr(csr);
+    int n;
+    {
+        const DeviceFloatEnv env;
+        float x[kLearnedMaxCond];
+        x[0] = (float)std::acos((double)std::fmin(1.0f, wi_local[2]));
+        for (int i = 0; i < m->C - 1; ++i) x[1 + i] = cond_rest[i];
+        n = m->C == 2 ? learned_conditional<2>(rec, m->M, x, wi_local, keep, force, w, mm, cc)
+                      : learned_conditional<3>(rec, m->M, x, wi_local, keep, force, w, mm, cc);
+    }
     for (int j = 0; j < n; ++j) {
         weights[j] = w[j];
         for (int i = 0; i < 3; ++i) means[3 * j + i] = mm[3 * j + i];
@@ -685,8 +702,7 @@ int sdmm_bsdf_phong_host(const float* params, const float rho[3], const float wi
                          float value[3], float* pdf) {
     if (!params || params[0] != (float)kBsdfPhong || !rho || !wi || !wo || !value || !pdf)
         return fail(SDMM_E_INVALID, "sdmm_bsdf_phong_host: invalid argument (params of a kind-3 BSDF)");
-    const unsigned csr = _mm_getcsr();
-    _mm_setcsr(csr | 0x8040u);
+    const DeviceFloatEnv env;
     if (u) {
         float o[3] = {0.0f, 0.0f, 1.0f};
         phong_sample(wi, params, rho, u[0], u[1], o, value, pdf);
@@ -694,7 +710,6 @@ int sdmm_bsdf_phong_host(const float* params, const float rho[3], const float wi
     } else {
         *pdf = phong_eval_pdf(wi, wo, params, rho, value);
     }
-    _mm_setcsr(csr);
     return SDMM_OK;
 }
 
@@ -702,8 +717,7 @@ int sdmm_bsdf_roughdielectric_host(const float* params, const float spec_trans[3
                                    float wo[3], float value[3], float* pdf, float* eta_out) {
     if (!params || params[0] != (float)kBsdfDielectric || !spec_trans || !wi || !wo || !value || !pdf || !eta_out)
         return fail(SDMM_E_INVALID, "sdmm_bsdf_roughdielectric_host: invalid argument (params of a kind-4 BSDF)");
-    const unsigned csr = _mm_getcsr();
-    _mm_setcsr(csr | 0x8040u);
+    const DeviceFloatEnv env;
     if (u) {
         float o[3];
         roughdielectric_sample(wi, params, spec_trans, u[0], u[1], u[2], o, value, pdf, eta_out);
@@ -712,7 +726,6 @@ int sdmm_bsdf_roughdielectric_host(const float* params, const float spec_trans[3
         *pdf = roughdielectric_eval_pdf(wi, wo, params, spec_trans, value);
         *eta_out = roughdielectric_crossed_eta(wi, wo, params);
     }
-    _mm_setcsr(csr);
     return SDMM_OK;
 }
 
@@ -736,8 +749,7 @@ int sdmm_bsdf_smooth_host(const float* params, const float spec_trans[3], const 
         return fail(SDMM_E_INVALID, "sdmm_bsdf_smooth_host: invalid argument (params of a kind-5 or kind-6 BSDF)");
     const float none[3] = {0.0f, 0.0f, 0.0f};
     const float* st = spec_trans ? spec_trans : none;
-    const unsigned csr = _mm_getcsr();
-    _mm_setcsr(csr | 0x8040u);
+    const DeviceFloatEnv env;
     if (u) {
         float o[3];
         smooth_sample(wi, params, st, u[0], o, value, pdf, eta_out);
@@ -745,7 +757,6 @@ int sdmm_bsdf_smooth_host(const float* params, const float spec_trans[3], const 
     } else {
         *pdf = smooth_eval_pdf(wi, wo, params, st, value, eta_out);
     }
-    _mm_setcsr(csr);
     return SDMM_OK;
 }
 
@@ -766,18 +777,7 @@ void sdmm_scene_destroy(sdmm_scene* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
-    if (s->dquads) (void)hipFree(s->dquads);
-    if (s->drefl) (void)hipFree(s->drefl);
-    if (s->dbpar) (void)hipFree(s->dbpar);
-    if (s->dlmod) (void)hipFree(s->dlmod);
-    if (s->dlmod_nd) (void)hipFree(s->dlmod_nd);
-    if (s->dtwosided) (void)hipFree(s->dtwosided);
-    if (s->drad) (void)hipFree(s->drad);
-    if (s->dnodes) (void)hipFree(s->dnodes);
-    if (s->dtris) (void)hipFree(s->dtris);
-    if (s->dhits) (void)hipFree(s->dhits);
-    if (s->dshade) (void)hipFree(s->dshade);
-    if (s->denv) (void)hipFree(s->denv);
+    for (void* p : s->owned) (void)hipFree(p);
     if (s->buf) (void)hipFree(s->buf);
     if (s->lt) (void)hipFree(s->lt);
     if (s->hcount) (void)hipHostFree(s->hcount);
@@ -818,27 +818,10 @@ int sdmm_scene_intersect_host_levels(const sdmm_scene_desc* desc, int max_levels
                                      const float* d, float mint, float maxt, int mode, int32_t* prim, float* t) {
     if (!desc || max_levels < 0 || nq < 0 || (mode != 0 && mode != 1) || (nq > 0 && (!o || !d || !prim || !t)))
         return fail(SDMM_E_INVALID, "sdmm_scene_intersect_host: invalid argument (mode 0 or 1)");
-    std::vector<QuadDev> qs;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    int rc = prep_quads(desc, "sdmm_scene_intersect_host", &qs, mn, mx);
-    if (rc) return rc;
-    MeshBvh mesh;
-    if (desc->n_triangles > 0) {
-        rc = prep_mesh(desc, "sdmm_scene_intersect_host", max_levels, &mesh);
-        if (rc) return rc;
-    }
-    // the device's float environment: denormals flushed (-fgpu-flush-denormals-to-zero)
-    const unsigned csr = _mm_getcsr();
-    _mm_setcsr(csr | 0x8040u);
-    const int nquads = (int)qs.size();
-    for (int64_t i = 0; i < nq; ++i) {
-        float tb;
-        int best = quads_closest(qs.data(), nquads, o + 3 * i, d + 3 * i, mint, maxt, tb);
-        if (desc->n_triangles > 0) mesh_closest_host(mesh, nquads, mode, o + 3 * i, d + 3 * i, mint, maxt, best, tb);
-        prim[i] = best;
-        t[i] = tb;
-    }
-    _mm_setcsr(csr);
+    HostScene hs;
+    if (const int rc = build_host_scene(desc, "sdmm_scene_intersect_host", max_levels, &hs)) return rc;
+    const DeviceFloatEnv env;
+    for (int64_t i = 0; i < nq; ++i) prim[i] = closest(hs, mode, o + 3 * i, d + 3 * i, mint, maxt, t + i);
     return SDMM_OK;
 }
 
@@ -860,35 +843,20 @@ int sdmm_scene_shading_host(const sdmm_scene_desc* desc, int64_t nq, const float
                             float maxt, int mode, int32_t* prim, float* t, float* ns, float* ng) {
     if (!desc || nq < 0 || (mode != 0 && mode != 1) || (nq > 0 && (!o || !d || !prim || !t || !ns || !ng)))
         return fail(SDMM_E_INVALID, "sdmm_scene_shading_host: invalid argument (mode 0 or 1)");
-    std::vector<QuadDev> qs;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    int rc = prep_quads(desc, "sdmm_scene_shading_host", &qs, mn, mx);
-    if (rc) return rc;
-    MeshBvh mesh;
-    if (desc->n_triangles > 0) {
-        rc = prep_mesh(desc, "sdmm_scene_shading_host", 0, &mesh);
-        if (rc) return rc;
-    }
+    HostScene hs;
+    if (const int rc = build_host_scene(desc, "sdmm_scene_shading_host", 0, &hs)) return rc;
     // the scene as hit_normals reads it, on host arrays
     SceneDev S{};
-    S.quads = qs.data();
-    S.n_quads = (int)qs.size();
-    S.hits = mesh.hits.data();
-    const MeshShade* shade = mesh.shade.empty() ? nullptr : mesh.shade.data();
-    // the device's float environment: denormals flushed (-fgpu-flush-denormals-to-zero)
-    const unsigned csr = _mm_getcsr();
-    _mm_setcsr(csr | 0x8040u);
+    S.quads = hs.quads.data();
+    S.n_quads = (int)hs.quads.size();
+    S.hits = hs.mesh.hits.data();
+    const MeshShade* shade = hs.mesh.shade.empty() ? nullptr : hs.mesh.shade.data();
+    const DeviceFloatEnv env;
     for (int64_t i = 0; i < nq; ++i) {
-        float tb;
-        int best = quads_closest(qs.data(), S.n_quads, o + 3 * i, d + 3 * i, mint, maxt, tb);
-        if (desc->n_triangles > 0)
-            mesh_closest_host(mesh, S.n_quads, mode, o + 3 * i, d + 3 * i, mint, maxt, best, tb);
-        prim[i] = best;
-        t[i] = tb;
+        prim[i] = closest(hs, mode, o + 3 * i, d + 3 * i, mint, maxt, t + i);
         for (int a = 0; a < 3; ++a) ns[3 * i + a] = ng[3 * i + a] = 0.0f;
-        if (best >= 0) hit_normals(S, shade, best, o + 3 * i, d + 3 * i, ns + 3 * i, ng + 3 * i);
+        if (prim[i] >= 0) hit_normals(S, shade, prim[i], o + 3 * i, d + 3 * i, ns + 3 * i, ng + 3 * i);
     }
-    _mm_setcsr(csr);
     return SDMM_OK;
 }
 
@@ -909,11 +877,8 @@ int sdmm_env_eval_host(const sdmm_scene_desc* desc, int64_t nq, const float* d, 
     const int rc = prep_env(desc, "sdmm_env_eval_host", &env);
     if (rc) return rc;
     env.texels = desc->env_pixels;   // [h][w][3], read in place
-    // the device's float environment: denormals flushed (-fgpu-flush-denormals-to-zero)
-    const unsigned csr = _mm_getcsr();
-    _mm_setcsr(csr | 0x8040u);
+    const DeviceFloatEnv flush;
     for (int64_t i = 0; i < nq; ++i) env_eval<false>(env, d + 3 * i, rgb + 3 * i);
-    _mm_setcsr(csr);
     return SDMM_OK;
 }
 

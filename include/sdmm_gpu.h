@@ -777,6 +777,25 @@ int sdmm_bsdf_smooth_host(const float* params, const float spec_trans[3], const 
 int sdmm_bsdf_smooth_device(const float* params, const float spec_trans[3], int64_t nq, const float* const wi[3],
                             const float* const* u, float* const wo[3], float* const value[3], float* pdf,
                             float* eta_out, void* hip_stream);
+/* An RGB bitmap texture (<texture type="bitmap">, textures/bitmap.cpp) for
+ * sdmm_scene_desc.textures.  pixels: host array [height][width][3] of linear
+ * RGB floats, texel (x, y) at 3 * (y * width + x), row 0 is v = 0 -- no flip,
+ * no gamma, no fromLinearRGB: the caller decodes.  filter: 0 bilinear
+ * (MIPMap::evalBilinear on level 0; also what the reference's EWA and
+ * trilinear textures take without ray differentials), 1 nearest (evalBox).
+ * wrap_u, wrap_v: 0 repeat, 1 clamp, 2 mirror, 3 zero, 4 one (wrapModeU /
+ * wrapModeV; evalTexel, render/mipmap.h:503-563).  uv_scale, uv_offset: the
+ * lookup is at its.uv * uv_scale + uv_offset (librender/texture.cpp:112-121);
+ * a uv_scale of 0 is rejected, so that a texture zeroed except for its size
+ * and pixels is not valid by accident (Mitsuba's default is 1). */
+typedef struct {
+    int width, height;
+    const float* pixels;
+    int filter;
+    int wrap_u, wrap_v;
+    float uv_scale[2];
+    float uv_offset[2];
+} sdmm_texture;
 typedef struct {
     int n_quads;
     const float* quads;
@@ -863,8 +882,8 @@ typedef struct {
      *                     when it is set, also without a quad `emitter`)
      *   tri_flip_normals  nullable
      * The normal is the face normal normalize((p1 - p0) x (p2 - p0)), negated
-     * where flipped (vertex normals: mesh_normals below).  UVs, textures and
-     * instancing are not supported.  n_quads may be 0 with triangles.
+     * where flipped (vertex normals: mesh_normals below; UVs and textures:
+     * mesh_uvs below).  Instancing is not supported.  n_quads may be 0 with triangles.
      * Primitive ids: quads 0 .. n_quads-1, triangle i is n_quads + i; the
      * learned-BSDF row of a hit is still its bsdf index, and the scene AABB
      * of sdmm_scene_normalization includes every mesh vertex.
@@ -943,7 +962,7 @@ typedef struct {
      * kind-4 or kind-5 BSDF ("Only materials without a transmission component
      * can be nested", :106-108).
      * Not supported: the two-child form (m_nestedBRDF[1] != [0]; there getDMM
-     * always asks child 0, :146), textures, two-sided emitters (with
+     * always asks child 0, :146), two-sided emitters (with
      * mesh_normals the stored normal n above is the hit's shading normal ns); the Mitsuba plugin does not run the device Li, so
      * it takes no such flag. */
     const int32_t* bsdf_twosided;
@@ -980,6 +999,61 @@ typedef struct {
      * SDMM_E_INVALID (with a message): mesh_normals set without triangles; a
      * non-finite normal; a normal of length 0 (all three components 0). */
     const float* mesh_normals;
+    /* Bitmap textures on reflectances (every field below is appended after
+     * mesh_normals; the zero-initialise rule below covers older callers: all
+     * NULL / 0 and every rule above holds, bit for bit, with the kernels a
+     * scene launched before).
+     *   mesh_uvs      nullable: texture coordinates of the mesh, 2 floats per
+     *                 mesh vertex.  At a hit on triangle (i0, i1, i2) with the
+     *                 triangle test's own u, v: its.uv = t[i0] b.x + t[i1] b.y
+     *                 + t[i2] b.z, b = (1 - u - v, u, v); without mesh_uvs
+     *                 its.uv = (u, v) (render/skdtree.h:399-405).  On a quad
+     *                 its.uv = (a, b), the two parametric coordinates of the
+     *                 hit along e1 and e2, p0 at (0, 0) (shapes/rectangle.cpp:
+     *                 163 with p0 as the local (-1, -1) corner).
+     *   n_textures, textures
+     *                 the scene's bitmaps (sdmm_texture above)
+     *   bsdf_texture  nullable: n_bsdfs entries, the texture that replaces
+     *                 BSDF b's reflectance row at every hit, -1 = none.  The
+     *                 row is diffuse.cpp's reflectance (kind 0) and the
+     *                 diffuseReflectance of plastic.cpp (kind 1) and phong.cpp
+     *                 (kind 3); the value is Texture2D::eval(its, false)
+     *                 (librender/texture.cpp:112-121: uv * uv_scale +
+     *                 uv_offset) over BitmapTexture::eval(uv) (textures/
+     *                 bitmap.cpp:431-454): MIPMap::evalBilinear, or evalBox
+     *                 with the nearest filter, on the full-resolution level
+     *                 (render/mipmap.h:503-596).  A hit whose texel is black
+     *                 (with a zero specular reflectance) ends the path, as a
+     *                 zero reflectance row does.
+     * The constant bsdf_params stay the caller's: Phong's and plastic's
+     * specular sampling weights come from the texture's average
+     * (phong.cpp:146-148), as does configure()'s energy scaling.  Phong's
+     * learned condition reads the specular reflectance and the exponent
+     * (phong.cpp:82-84), neither textured here: product sampling is unchanged.
+     * Departures: every hit takes eval(uv) -- there are no ray differentials
+     * here, so not the EWA lookup Mitsuba gives its camera rays (bitmap.cpp:
+     * 486); a non-finite uv gives 0 (evalBilinear's guard) in nearest mode
+     * too; a texel coordinate that does not fit int32 gives 0 (floorToInt is
+     * undefined there).
+     * Not supported: a textured specular reflectance, exponent, alpha or
+     * radiance; EWA / trilinear filtering; computeShadingFrame's UV tangents
+     * (the shading frame stays Frame(ns)); procedural textures; image-file
+     * reading.
+     * SDMM_E_INVALID (with a message; these checks come after every other):
+     * mesh_uvs without triangles or with a non-finite value; n_textures < 0
+     * or textures NULL with n_textures > 0; bsdf_texture without textures; a
+     * texture with width or height < 1, NULL pixels, an unknown filter or
+     * wrap, a zero or non-finite uv_scale, a non-finite uv_offset, a
+     * non-finite or negative texel; more than 2^26 texels in all; a
+     * bsdf_texture entry outside -1 .. n_textures - 1, or set on a BSDF of
+     * kind 2 (its row is unused) or 4, 5, 6 (which carry no textures).
+     * (The reference reads any bitmap, negative and non-finite values
+     * included; rejecting those here is this library's choice, the one it
+     * makes for the environment map's texels and the reflectance rows.) */
+    const float* mesh_uvs;
+    int n_textures;
+    const sdmm_texture* textures;
+    const int32_t* bsdf_texture;
 } sdmm_scene_desc;
 /* The descriptor has grown across ABI revisions (bsdf_params was appended):
  * zero-initialise it (`sdmm_scene_desc d = {0};` / `memset`) before filling
@@ -1098,6 +1172,25 @@ int sdmm_scene_shading(const sdmm_scene* s, int64_t nq, const float* const o[3],
  * serves this entry, the device entry and the Li kernels, bitwise alike. */
 int sdmm_scene_shading_host(const sdmm_scene_desc* desc, int64_t nq, const float* o, const float* d, float mint,
                             float maxt, int mode, int32_t* prim, float* t, float* ns, float* ng);
+/* sdmm_scene_intersect extended by the hit's texture coordinates and the
+ * effective reflectance of its BSDF, as the Li kernels compute them
+ * (sdmm_scene_desc.mesh_uvs, textures, bsdf_texture): uv two device planes
+ * (its.uv, before uv_scale and uv_offset), rgb three -- the texture's value at
+ * the hit, or the BSDF's reflectance row where it carries no texture (the uv
+ * is reported all the same); zeros on a miss.  Asynchronous on hip_stream.
+ * (A scene with triangles created with neither mesh_uvs nor textures holds no
+ * per-triangle table: a hit on its mesh then finds its triangle by a linear
+ * search -- the same answer, slowly.) */
+int sdmm_scene_texture(const sdmm_scene* s, int64_t nq, const float* const o[3], const float* const d[3], float mint,
+                       float maxt, int mode, int32_t* prim, float* t, float* const uv[2], float* const rgb[3],
+                       void* hip_stream);
+/* The same entirely on the host (no HIP call: runs without a GPU) from a
+ * description -- o, d host arrays [nq][3], uv [nq][2], rgb [nq][3].  Validates
+ * the geometry and the texture fields as sdmm_scene_create does (bsdf_params
+ * is read for the kinds only); one source (csrc/texture.h) serves this entry,
+ * the device entry and the Li kernels, bitwise alike. */
+int sdmm_scene_texture_host(const sdmm_scene_desc* desc, int64_t nq, const float* o, const float* d, float mint,
+                            float maxt, int mode, int32_t* prim, float* t, float* uv, float* rgb);
 /* evalEnvironment of the scene's environment emitter (sdmm_scene_desc's env
  * fields) for nq directions: d, rgb three device planes each (the direction
  * is used as given; rgb: the radiance, 0 for a scene without an environment).

@@ -181,6 +181,10 @@ def lib():
                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdmm_scene_shading_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sdmm_scene_texture.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sdmm_scene_texture_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdmm_env_eval.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdmm_env_eval_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.sdmm_mesh_bvh_dump.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
@@ -305,6 +309,7 @@ EXPORTED_SYMBOLS = [
     "sdmm_bsdf_smooth_host", "sdmm_bsdf_smooth_device",
     "sdmm_scene_intersect", "sdmm_scene_intersect_host", "sdmm_scene_intersect_host_levels",
     "sdmm_mesh_bvh_dump", "sdmm_scene_shading", "sdmm_scene_shading_host",
+    "sdmm_scene_texture", "sdmm_scene_texture_host",
     "sdmm_env_eval", "sdmm_env_eval_host",
     "sdmm_read_exr", "sdmm_film_create", "sdmm_film_destroy", "sdmm_film_add_pass", "sdmm_film_passes",
     "sdmm_film_pass_stats", "sdmm_film_resolve", "sdmm_film_errors", "sdmm_film_variance", "sdmm_film_reset",
@@ -1483,7 +1488,66 @@ class _SceneDesc(C.Structure):
                 ("env_kind", C.c_int), ("env_radiance", C.c_float * 3), ("env_width", C.c_int),
                 ("env_height", C.c_int), ("env_pixels", C.c_void_p), ("env_scale", C.c_float),
                 ("env_world_to_local", C.c_float * 9), ("bsdf_twosided", C.c_void_p),
-                ("mesh_normals", C.c_void_p)]
+                ("mesh_normals", C.c_void_p), ("mesh_uvs", C.c_void_p), ("n_textures", C.c_int),
+                ("textures", C.c_void_p), ("bsdf_texture", C.c_void_p)]
+
+
+class _Texture(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("pixels", C.c_void_p), ("filter", C.c_int),
+                ("wrap_u", C.c_int), ("wrap_v", C.c_int), ("uv_scale", C.c_float * 2), ("uv_offset", C.c_float * 2)]
+
+
+TEXTURE_FILTERS = {"bilinear": 0, "nearest": 1}
+TEXTURE_WRAPS = {"repeat": 0, "clamp": 1, "mirror": 2, "zero": 3, "one": 4}
+
+
+def _fill_textures(d, desc, keep):
+    """The texture fields of a _SceneDesc from a description dict: mesh_uvs
+    [n_mesh_vertices, 2]; textures, a list of dicts {"pixels": float32
+    [height, width, 3] linear RGB (row 0 is v = 0), "filter": "bilinear"
+    (default) / "nearest" or 0 / 1, "wrap_u", "wrap_v": "repeat" (default) /
+    "clamp" / "mirror" / "zero" / "one" or 0 .. 4, "uv_scale" (default 1; a
+    number or a pair), "uv_offset" (default 0)}; bsdf_texture, one index per
+    BSDF (-1: none)."""
+    def code(value, names, what):
+        if isinstance(value, str):
+            if value not in names:
+                raise SDMMError(f"a texture's {what}: one of {sorted(names)} or its number, not {value!r}")
+            return names[value]
+        return int(value)
+    if desc.get("mesh_uvs") is not None:
+        if np.asarray(desc["mesh_uvs"]).size != 2 * d.n_mesh_vertices:
+            raise SDMMError("mesh_uvs: 2 floats per mesh vertex")
+        keep["mesh_uvs"] = np.ascontiguousarray(desc["mesh_uvs"], np.float32)
+        d.mesh_uvs = keep["mesh_uvs"].ctypes.data
+    texs = desc.get("textures")
+    if texs:
+        tab = (_Texture * len(texs))()
+        for i, t in enumerate(texs):
+            px = np.ascontiguousarray(t["pixels"], np.float32)
+            if px.ndim != 3 or px.shape[2] != 3:
+                raise SDMMError("a texture's pixels: an array [height, width, 3]")
+            keep[f"texture_pixels_{i}"] = px
+            tab[i].height, tab[i].width, tab[i].pixels = int(px.shape[0]), int(px.shape[1]), px.ctypes.data
+            tab[i].filter = code(t.get("filter", 0), TEXTURE_FILTERS, "filter")
+            for key in ("wrap_u", "wrap_v"):
+                setattr(tab[i], key, code(t.get(key, 0), TEXTURE_WRAPS, key))
+            sc = np.broadcast_to(np.asarray(t.get("uv_scale", 1.0), np.float32), (2,))
+            of = np.broadcast_to(np.asarray(t.get("uv_offset", 0.0), np.float32), (2,))
+            for a in range(2):
+                tab[i].uv_scale[a], tab[i].uv_offset[a] = float(sc[a]), float(of[a])
+        keep["textures"] = tab
+        d.n_textures = len(texs)
+        d.textures = C.cast(tab, C.c_void_p)
+    if desc.get("bsdf_texture") is not None:
+        if np.asarray(desc["bsdf_texture"]).size != d.n_bsdfs:
+            raise SDMMError("bsdf_texture: one entry per BSDF")
+        keep["bsdf_texture"] = np.ascontiguousarray(desc["bsdf_texture"], np.int32)
+        d.bsdf_texture = keep["bsdf_texture"].ctypes.data
+        # (the kinds, which the entry's validation reads)
+        if desc.get("bsdf_params") is not None:
+            keep["bsdf_params"] = np.ascontiguousarray(desc["bsdf_params"], np.float32)
+            d.bsdf_params = keep["bsdf_params"].ctypes.data
 
 
 def _fill_geometry(d, desc, keep):
@@ -1527,6 +1591,7 @@ def _fill_geometry(d, desc, keep):
         d.bsdf_twosided = arr("bsdf_twosided", np.int32).ctypes.data
         if desc.get("bsdf_params") is not None:
             d.bsdf_params = arr("bsdf_params", np.float32).ctypes.data
+    _fill_textures(d, desc, keep)
     _fill_env(d, desc, keep)
 
 
@@ -1605,6 +1670,28 @@ def shading_host(desc, o, d, mint=1e-4, maxt=float("inf"), mode=0):
     _check(lib().sdmm_scene_shading_host(C.byref(sd), len(o), o.ctypes.data, dd.ctypes.data, float(mint), float(maxt),
                                          int(mode), prim.ctypes.data, t.ctypes.data, ns.ctypes.data, ng.ctypes.data))
     return prim, t, ns, ng
+
+
+def texture_host(desc, o, d, mint=1e-4, maxt=float("inf"), mode=0):
+    """sdmm_scene_texture_host: intersect_host plus the hit's texture
+    coordinates and the effective reflectance of its BSDF as the Li kernels
+    compute them (desc["mesh_uvs"], "textures", "bsdf_texture"), entirely on
+    the host (no GPU).  (prim int32[nq], t float32[nq], uv float32[nq, 2], rgb
+    float32[nq, 3]); zeros on a miss, the BSDF's reflectance row where it
+    carries no texture."""
+    sd, keep = _SceneDesc(), {}
+    _fill_geometry(sd, desc, keep)
+    o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+    dd = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+    if o.shape != dd.shape:
+        raise SDMMError("o and d: [nq, 3] each")
+    prim = np.empty(len(o), np.int32)
+    t = np.empty(len(o), np.float32)
+    uv = np.empty((len(o), 2), np.float32)
+    rgb = np.empty((len(o), 3), np.float32)
+    _check(lib().sdmm_scene_texture_host(C.byref(sd), len(o), o.ctypes.data, dd.ctypes.data, float(mint), float(maxt),
+                                         int(mode), prim.ctypes.data, t.ctypes.data, uv.ctypes.data, rgb.ctypes.data))
+    return prim, t, uv, rgb
 
 
 def mesh_bvh_dump(desc, max_levels=0):
@@ -2130,6 +2217,32 @@ class Scene:
                                         C.cast(P3(*[x.data_ptr() for x in ng]), C.c_void_p),
                                         C.c_void_p(int(s_.cuda_stream) or None)))
         return prim, t, ns, ng
+
+    def texture(self, o, d, mint=1e-4, maxt=float("inf"), mode=0, stream=None):
+        """sdmm_scene_texture: intersect plus the hit's texture coordinates
+        and the effective reflectance of its BSDF as the Li kernels compute
+        them -- o, d: 3 float32 device tensors of nq each.  (prim int32[nq], t
+        float32[nq], uv: 2, rgb: 3 float32 device tensors; zeros on a miss);
+        bitwise texture_host's."""
+        import torch
+        nq = o[0].numel()
+        dev = o[0].device
+        for t_ in list(o) + list(d):
+            if t_.numel() != nq or t_.dtype != torch.float32 or not t_.is_contiguous() or t_.device != dev:
+                raise SDMMError("planes: contiguous float32 device tensors of one value per ray")
+        prim = torch.empty(nq, device=dev, dtype=torch.int32)
+        t = torch.empty(nq, device=dev)
+        uv = [torch.empty(nq, device=dev) for _ in range(2)]
+        rgb = [torch.empty(nq, device=dev) for _ in range(3)]
+        s_ = torch.cuda.current_stream(dev) if stream is None else stream
+        P3 = C.c_void_p * 3
+        _check(lib().sdmm_scene_texture(self.h, nq, C.cast(P3(*[x.data_ptr() for x in o]), C.c_void_p),
+                                        C.cast(P3(*[x.data_ptr() for x in d]), C.c_void_p), float(mint), float(maxt),
+                                        int(mode), prim.data_ptr(), t.data_ptr(),
+                                        C.cast((C.c_void_p * 2)(*[x.data_ptr() for x in uv]), C.c_void_p),
+                                        C.cast(P3(*[x.data_ptr() for x in rgb]), C.c_void_p),
+                                        C.c_void_p(int(s_.cuda_stream) or None)))
+        return prim, t, uv, rgb
 
     def env_eval(self, d, stream=None):
         """sdmm_env_eval: the environment emitter's radiance for directions on

@@ -33,8 +33,9 @@
 // guide and saves no vertex), each non-transmitting kind optionally under the
 // single-child twosided adapter (twosided.cpp, SceneDev::twosided: a hit from
 // behind runs the nested BSDF in (s, t, -n) of Frame(n), saves -n with its
-// vertex and hands the product F = [s t -n]; the two-child form, textures and
-// two-sided emitters are not done),
+// vertex and hands the product F = [s t -n]; the two-child form and two-sided
+// emitters are not done), a bitmap texture in place of a diffuse, plastic or
+// Phong BSDF's reflectance row (texture.h: the TEX variants),
 // one-sided area emitters (area.cpp: Le = radiance on the normal side) and an
 // optional environment emitter (envmap.h: constant or lat-long map, seen by
 // every ray that leaves the scene).  No NEE (the plugin's
@@ -113,13 +114,27 @@ __device__ __forceinline__ int prim_emitter(const SceneDev& S, int q) {
 // They take the normals' record as one more, last argument -- the parameter
 // pack Nrm = {NormalsDev}; the variants every other scene runs have an empty
 // pack, so their arguments are what they always were.
-__device__ __forceinline__ NormalsDev nrm_arg(NormalsDev n) { return n; }
+// TEX: the variants for a scene whose BSDFs carry bitmap textures (texture.h),
+// the camera, query and shade kernels': TexDev rides in the same pack, after
+// NormalsDev where both are -- Nrm = {}, {NormalsDev}, {TexDev} or {NormalsDev,
+// TexDev}.  pack_has<T>: the pack holds a T; pack_get<T>: it.
+template <class T, class... X>
+constexpr bool pack_has = (std::is_same_v<T, X> || ...);
+template <class T, class A, class... X>
+__device__ __forceinline__ T pack_get(A a, X... x) {
+    if constexpr (std::is_same_v<T, A>) return a;
+    else return pack_get<T>(x...);
+}
+template <class... X>
+__device__ __forceinline__ NormalsDev nrm_arg(X... x) { return pack_get<NormalsDev>(x...); }
+template <class... X>
+__device__ __forceinline__ TexDev tex_arg(X... x) { return pack_get<TexDev>(x...); }
 // The current hit's shading normal: NRM from the path's planes, where the
 // kernel that traced the ray left it -- otherwise the primitive's face normal,
 // fetched by id as ever.  buf: the caller's three floats (unused without NRM).
 template <bool MESH, class... Nrm>
 __device__ __forceinline__ const float* path_ns(const SceneDev& S, int64_t i, int q, float buf[3], Nrm... nrm) {
-    if constexpr (sizeof...(Nrm) != 0) {
+    if constexpr (pack_has<NormalsDev, Nrm...>) {
         const NormalsDev N = nrm_arg(nrm...);
         buf[0] = N.nsx[i]; buf[1] = N.nsy[i]; buf[2] = N.nsz[i];
         return buf;
@@ -130,6 +145,28 @@ __device__ __forceinline__ const float* path_ns(const SceneDev& S, int64_t i, in
 __device__ __forceinline__ void store_normals(const NormalsDev& N, int64_t i, const float ns[3], const float ng[3]) {
     N.nsx[i] = ns[0]; N.nsy[i] = ns[1]; N.nsz[i] = ns[2];
     N.ngx[i] = ng[0]; N.ngy[i] = ng[1]; N.ngz[i] = ng[2];
+}
+// The current hit's effective reflectance: TEX from the path's planes, where
+// the kernel that traced the ray left it (the texture's value at the hit, or
+// the row of an untextured BSDF) -- otherwise BSDF qb's row, as ever.
+template <class... Nrm>
+__device__ __forceinline__ const float* path_rho(const SceneDev& S, int64_t i, int qb, float buf[3], Nrm... nrm) {
+    if constexpr (pack_has<TexDev, Nrm...>) {
+        const TexDev T = tex_arg(nrm...);
+        buf[0] = T.rr[i]; buf[1] = T.rg[i]; buf[2] = T.rb[i];
+        return buf;
+    } else {
+        return S.refl + 3 * qb;
+    }
+}
+// The kernel that traced a ray (camera, shade) leaves the hit's effective
+// reflectance in the path's planes: BSDF qb's texture at the hit's uv, or its
+// row -- one lookup (four texels at most) per hit, coalesced reads afterwards.
+__device__ __forceinline__ void store_reflectance(const SceneDev& S, const TexDev& T, int64_t i, int qb,
+                                                  const float uv[2]) {
+    float rgb[3];
+    hit_reflectance<true>(S.refl, T.tex, T.bsdf_tex, qb, uv, rgb);
+    T.rr[i] = rgb[0]; T.rg[i] = rgb[1]; T.rb[i] = rgb[2];
 }
 // the MESH kernels' traversal stack: kBvhStack levels x 256 threads of LDS
 #define LI_MESH_STACK(stack)                              \
@@ -243,10 +280,13 @@ __device__ __forceinline__ void record_radiance(const PathsDev& P, int64_t p, in
 // ns / ng are worked out here, once, and left in the path's planes; emission
 // is seen on the shading normal's side (dot(its.shFrame.n, d) <= 0 gives 0,
 // emitters/area.cpp:105).
+// TEX: the variant for a scene with textured BSDFs (texture.h): the hit's uv
+// and its BSDF's effective reflectance are worked out here, once, and left in
+// the path's planes.
 template <bool MESH, bool ENV, class... Nrm>
 __global__ void __launch_bounds__(256)
 li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed, Nrm... nrm) {
-    constexpr bool NRM = sizeof...(Nrm) != 0;
+    constexpr bool NRM = pack_has<NormalsDev, Nrm...>, TEX = pack_has<TexDev, Nrm...>;
     static_assert(!NRM || MESH, "NRM: a MESH variant");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.P) return;
@@ -277,10 +317,22 @@ li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed, 
         float hns[3], hng[3];
         const float* qn;
         if constexpr (NRM) {
-            hit_normals(S, nrm_arg(nrm...).shade, q, o, d, hns, hng);
+            if constexpr (TEX) {
+                // (the triangle test on the winner runs once for both)
+                float uv[2];
+                hit_normals_uv(S, nrm_arg(nrm...).shade, tex_arg(nrm...).mesh_uv, q, o, d, hns, hng, uv);
+                store_reflectance(S, tex_arg(nrm...), i, prim_bsdf<MESH>(S, q), uv);
+            } else {
+                hit_normals(S, nrm_arg(nrm...).shade, q, o, d, hns, hng);
+            }
             store_normals(nrm_arg(nrm...), i, hns, hng);
             qn = hns;
         } else {
+            if constexpr (TEX) {
+                float uv[2];
+                hit_uv(S.quads, S.n_quads, tex_arg(nrm...).mesh_uv, q, o, d, uv);
+                store_reflectance(S, tex_arg(nrm...), i, prim_bsdf<MESH>(S, q), uv);
+            }
             qn = prim_n<MESH>(S, q);
         }
         const int qe = prim_emitter<MESH>(S, q);
@@ -309,11 +361,13 @@ li_camera_kernel(SceneDev S, PathsDev P, int64_t path0, int spp, uint64_t seed, 
 // NRM: with vertex normals everything here runs on the hit's shading normal,
 // and strictNormals' first test ends the path whose wi lies on different sides
 // of the two normals ((wi . ng)(wi . ns) < 0, sdmm_proc.cpp:688-691).
+// TEX: the reflectance of kinds 0, 1 and 3 is the hit's own, from the path's
+// planes; the zero-reflectance rule then holds per hit.
 template <bool PHONG, bool DIEL, bool MESH, class... Nrm>
 __global__ void __launch_bounds__(256)
 li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int max_depth, int guided,
                 float h, uint64_t seed, Nrm... nrm) {
-    constexpr bool NRM = sizeof...(Nrm) != 0;
+    constexpr bool NRM = pack_has<NormalsDev, Nrm...>, TEX = pack_has<TexDev, Nrm...>;
     static_assert(!NRM || MESH, "NRM: a MESH variant");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.P) return;
@@ -325,6 +379,7 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     float n[3] = {0, 0, 0}, wi[3] = {0, 0, 0};
     bool pure_delta = false;            // a kind-5 or kind-6 hit (DIEL)
     bool back = false;                  // a two-sided BSDF met from behind
+    float rbuf[3];                      // (TEX: the hit's reflectance)
     if (live) {
         const float* qn = prim_n<MESH>(S, q);
         const int qb = prim_bsdf<MESH>(S, q);
@@ -339,7 +394,9 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
                 if (dot3(wi, ng) * dot3(wi, n) < 0.0f) live = false;
             }
         }
-        const float* rho = S.refl + 3 * qb;
+        // (TEX: the hit's own reflectance, so a hit on a black texel ends the
+        // path here as bsdfWeight.isZero() does in the reference)
+        const float* rho = path_rho(S, i, qb, rbuf, nrm...);
         const float* bp = S.bpar ? S.bpar + kBsdfParams * qb : nullptr;
         const int kind = bp ? (int)bp[0] : kBsdfDiffuse;
         const bool zero_spec = kind == kBsdfDiffuse || (bp[1] == 0.0f && bp[2] == 0.0f && bp[3] == 0.0f);
@@ -385,7 +442,7 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         // delta mirror lobe with probability probSpecular, else the cosine
         // hemisphere on the rescaled first coordinate; weight and pdf for the
         // shade kernel (a mixture bounce keeps the sampled lobe, :392-407)
-        const float* rho = S.refl + 3 * prim_bsdf<MESH>(S, q);
+        const float* rho = path_rho(S, i, prim_bsdf<MESH>(S, q), rbuf, nrm...);
         const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};   // Frame::toLocal
         const float Fi = fresnel_dielectric(wl[2], bp[4]);
         const float ps = plastic_prob_specular(Fi, bp[7]);
@@ -418,7 +475,7 @@ li_query_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         Q.bpdf[i] = bpdf;
     } else if (PHONG && bp && bp[0] == (float)kBsdfPhong) {
         // Phong::sample (phong.cpp:232-289); a void sample has weight 0
-        const float* rho = S.refl + 3 * prim_bsdf<MESH>(S, q);
+        const float* rho = path_rho(S, i, prim_bsdf<MESH>(S, q), rbuf, nrm...);
         const float wl[3] = {dot3(wi, s), dot3(wi, t), dot3(wi, n)};
         float bw[3], bpdf;
         phong_sample(wl, bp, rho, rng_uniform(seed, gp, stream, 0), rng_uniform(seed, gp, stream, 1), w, bw, &bpdf);
@@ -582,11 +639,13 @@ li_compact_kernel(SceneDev S, PathsDev P, QueryDev Q, const int32_t* __restrict_
 // hands wo back with its z flipped again (:137) -- so (wo . ng)(wo . ns)
 // whatever the side; without strictNormals neither test runs.  The new hit's
 // ns / ng are worked out after the trace and left in the path's planes.
+// TEX: the bounce weighs with the current hit's reflectance from the path's
+// planes; the new hit's is looked up after the roulette and left there.
 template <bool PHONG, bool DIEL, bool MESH, bool ENV, class... Nrm>
 __global__ void __launch_bounds__(256)
 li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, int rr_depth, float h,
                 uint64_t seed, int product, Nrm... nrm) {
-    constexpr bool NRM = sizeof...(Nrm) != 0;
+    constexpr bool NRM = pack_has<NormalsDev, Nrm...>, TEX = pack_has<TexDev, Nrm...>;
     static_assert(!NRM || MESH, "NRM: a MESH variant");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P.P) return;
@@ -604,7 +663,11 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         if (twosided_back(S, prim_bsdf<MESH>(S, pq), dot3(wi, n)))
             for (int a = 0; a < 3; ++a) n[a] = -n[a];
     }
-    const float* rho = S.refl + 3 * prim_bsdf<MESH>(S, pq);
+    // (TEX: the hit's own reflectance; a dielectric's row -- its
+    // transmittance -- carries no texture and is read as ever)
+    float rbuf[3];
+    const float* rho_row = S.refl + 3 * prim_bsdf<MESH>(S, pq);
+    const float* rho = path_rho(S, i, prim_bsdf<MESH>(S, pq), rbuf, nrm...);
     const int j = Q.slot[i];            // the path's guided query (-1: none, BSDF only)
     const int comp = j >= 0 ? Q.comp[j] : -1;
     const bool valid = comp != -1;      // validConditional (:368)
@@ -654,7 +717,7 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
             const float rd = 1.0f / (1.0f - bp[6]);
             const float k = cpdf * bp[5] * (1.0f - Fi) * (1.0f - Fo);
             for (int ch = 0; ch < 3; ++ch) {
-                const float f = up ? S.refl[3 * prim_bsdf<MESH>(S, pq) + ch] * rd * k : 0.0f;
+                const float f = up ? rho[ch] * rd * k : 0.0f;
                 weight[ch] = mis_pdf == 0.0f ? 0.0f : f * (1.0f / mis_pdf);
             }
         }
@@ -714,7 +777,7 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
             const float wol[3] = {dot3(wo, s), dot3(wo, t), dot3(wo, n)};
             const bool zero = (wo[0] == 0.0f && wo[1] == 0.0f && wo[2] == 0.0f) || !__builtin_isfinite(wol[2]);
             float f[3] = {0.0f, 0.0f, 0.0f};
-            const float bsdf_pdf = zero ? 0.0f : roughdielectric_eval_pdf(wil, wol, bp, rho, f);
+            const float bsdf_pdf = zero ? 0.0f : roughdielectric_eval_pdf(wil, wol, bp, rho_row, f);
             crossed = roughdielectric_crossed_eta(wil, wol, bp);
             mis_pdf = bsdf_pdf > 0.0f ? h * bsdf_pdf + (1.0f - h) * Q.pdf[j] : 0.0f;
             for (int ch = 0; ch < 3; ++ch) weight[ch] = mis_pdf == 0.0f ? 0.0f : f[ch] * (1.0f / mis_pdf);
@@ -771,11 +834,13 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
     const int q = intersect<MESH>(S, o, wo, kEpsilon, INFINITY, t, stack);
     float value[3] = {0.0f, 0.0f, 0.0f};
     float hns[3], hng[3];               // the new hit's normals (NRM)
+    float huv[2];                       // ... and its uv (NRM and TEX: from the same triangle test)
     if (q >= 0) {
         const int he = prim_emitter<MESH>(S, q);
         const float* hn;
         if constexpr (NRM) {
-            hit_normals(S, nrm_arg(nrm...).shade, q, o, wo, hns, hng);
+            if constexpr (!TEX) hit_normals(S, nrm_arg(nrm...).shade, q, o, wo, hns, hng);
+            else hit_normals_uv(S, nrm_arg(nrm...).shade, tex_arg(nrm...).mesh_uv, q, o, wo, hns, hng, huv);
             hn = hns;
         } else {
             hn = prim_n<MESH>(S, q);
@@ -832,6 +897,12 @@ li_shade_kernel(SceneDev S, PathsDev P, QueryDev Q, int64_t path0, int bounce, i
         P.px[i] = o[0] + t * wo[0]; P.py[i] = o[1] + t * wo[1]; P.pz[i] = o[2] + t * wo[2];
         P.quad[i] = q;
         if constexpr (NRM) store_normals(nrm_arg(nrm...), i, hns, hng);
+        // (TEX: the lookup here, for the paths that go on -- nothing of it is
+        // live over the bounce and the trace)
+        if constexpr (TEX) {
+            if constexpr (!NRM) hit_uv(S.quads, S.n_quads, tex_arg(nrm...).mesh_uv, q, o, wo, huv);
+            store_reflectance(S, tex_arg(nrm...), i, prim_bsdf<MESH>(S, q), huv);
+        }
     }
     P.depth[i] = live ? depth + 1 : -1;
 }
@@ -1007,15 +1078,22 @@ static void with_flag(bool flag, F f) {
 // nrm...) gets, as std::bool_constant values, PHONG = some BSDF is Phong, DIEL =
 // some is a dielectric or delta only, MESH = the scene has triangles, ENV = it
 // has an environment emitter (ENV_KERNEL: the camera and shade kernels; false
-// for the others), and the pack nrm = N with vertex normals (N.shade set: the
-// NRM variants, always MESH), nothing otherwise.  (The nesting -- NRM, ENV,
-// MESH, DIEL, PHONG, true first -- is the order the variants are instantiated
-// in, and so the order of the kernels in the code object.)
-template <bool ENV_KERNEL, class F>
-static void li_variant(const SceneDev& S, const NormalsDev& N, F launch) {
+// for the others), and the pack nrm: N with vertex normals (N.shade set: the
+// NRM variants, always MESH), then T with textured BSDFs (T.bsdf_tex set: the
+// TEX variants; TEX_KERNEL: the camera, query and shade kernels -- compact
+// reads nothing of T and has no such variant), nothing otherwise.  (The nesting -- NRM, ENV, MESH, DIEL,
+// PHONG, TEX, true first -- is the order the variants are instantiated in, and
+// so the order of the kernels in the code object.)
+template <bool ENV_KERNEL, bool TEX_KERNEL, class F>
+static void li_variant(const SceneDev& S, const NormalsDev& N, const TexDev& T, F launch) {
     const auto by_bsdfs = [&](auto env, auto mesh, auto... nrm) {
         with_flag(S.has_dielectric, [&](auto diel) {
-            with_flag(S.has_phong, [&](auto phong) { launch(phong, diel, mesh, env, nrm...); });
+            with_flag(S.has_phong, [&](auto phong) {
+                if constexpr (TEX_KERNEL) {
+                    if (T.bsdf_tex) return launch(phong, diel, mesh, env, nrm..., T);
+                }
+                launch(phong, diel, mesh, env, nrm...);
+            });
         });
     };
     const auto by_env = [&](auto next) {
@@ -1026,17 +1104,18 @@ static void li_variant(const SceneDev& S, const NormalsDev& N, F launch) {
     else by_env([&](auto env) { with_flag(S.has_mesh, [&](auto mesh) { by_bsdfs(env, mesh); }); });
 }
 
-hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, const NormalsDev& N, int64_t path0, int spp,
-                            uint64_t seed, hipStream_t st) {
-    li_variant<true>(S, N, [&](auto, auto, auto mesh, auto env, auto... nrm) {
+hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, const NormalsDev& N, const TexDev& T, int64_t path0,
+                            int spp, uint64_t seed, hipStream_t st) {
+    li_variant<true, true>(S, N, T, [&](auto, auto, auto mesh, auto env, auto... nrm) {
         hipLaunchKernelGGL((li_camera_kernel<mesh.value, env.value, decltype(nrm)...>), grid_for(P.P), dim3(256), 0, st,
                            S, P, path0, spp, seed, nrm...);
     });
     return hipGetLastError();
 }
-hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N, int64_t path0,
-                           int bounce, int max_depth, int guided, float h, uint64_t seed, hipStream_t st) {
-    li_variant<false>(S, N, [&](auto phong, auto diel, auto mesh, auto, auto... nrm) {
+hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N,
+                           const TexDev& T, int64_t path0, int bounce, int max_depth, int guided, float h,
+                           uint64_t seed, hipStream_t st) {
+    li_variant<false, true>(S, N, T, [&](auto phong, auto diel, auto mesh, auto, auto... nrm) {
         hipLaunchKernelGGL((li_query_kernel<phong.value, diel.value, mesh.value, decltype(nrm)...>), grid_for(P.P),
                            dim3(256), 0, st, S, P, Q, path0, bounce, max_depth, guided, h, seed, nrm...);
     });
@@ -1054,16 +1133,17 @@ hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDe
     hipError_t e = hipcub::DeviceSelect::Flagged(temp, temp_bytes, hipcub::CountingInputIterator<int32_t>(0), Q.live,
                                                  Q.idx, count_dev, (int)n, st);
     if (e != hipSuccess) return e;
-    li_variant<false>(S, N, [&](auto phong, auto diel, auto mesh, auto, auto... nrm) {
+    li_variant<false, false>(S, N, TexDev{}, [&](auto phong, auto diel, auto mesh, auto, auto... nrm) {
         hipLaunchKernelGGL((li_compact_kernel<phong.value, diel.value, mesh.value, decltype(nrm)...>), grid_for(n),
                            dim3(256), 0, st, S, P, Q, (const int32_t*)count_dev, product, nrm...);
     });
     return hipGetLastError();
 }
 
-hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N, int64_t path0,
-                           int bounce, int rr_depth, float h, uint64_t seed, int product, hipStream_t st) {
-    li_variant<true>(S, N, [&](auto phong, auto diel, auto mesh, auto env, auto... nrm) {
+hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N,
+                           const TexDev& T, int64_t path0, int bounce, int rr_depth, float h, uint64_t seed,
+                           int product, hipStream_t st) {
+    li_variant<true, true>(S, N, T, [&](auto phong, auto diel, auto mesh, auto env, auto... nrm) {
         hipLaunchKernelGGL((li_shade_kernel<phong.value, diel.value, mesh.value, env.value, decltype(nrm)...>),
                            grid_for(P.P), dim3(256), 0, st, S, P, Q, path0, bounce, rr_depth, h, seed, product, nrm...);
     });
@@ -1343,6 +1423,65 @@ hipError_t launch_scene_shading(const SceneDev& S, const MeshShade* shade, int64
     else
         hipLaunchKernelGGL(scene_shading_kernel<true>, grid_for(nq), dim3(256), 0, st, S, shade, nq, o[0], o[1],
                            o[2], d[0], d[1], d[2], mint, maxt, prim, t, ns[0], ns[1], ns[2], ng[0], ng[1], ng[2]);
+    return hipGetLastError();
+}
+
+// sdmm_scene_texture: sdmm_scene_intersect's search, then the hit's uv and the
+// effective reflectance of its BSDF as the Li kernels compute them (hit_uv,
+// hit_reflectance); zeros on a miss
+template <bool BRUTE>
+__global__ void __launch_bounds__(256)
+scene_texture_kernel(SceneDev S, TexDev T, int64_t nq, const float* __restrict__ o0, const float* __restrict__ o1,
+                     const float* __restrict__ o2, const float* __restrict__ d0, const float* __restrict__ d1,
+                     const float* __restrict__ d2, float mint, float maxt, int32_t* __restrict__ prim,
+                     float* __restrict__ t_out, float* __restrict__ uv0, float* __restrict__ uv1,
+                     float* __restrict__ r, float* __restrict__ g, float* __restrict__ b) {
+    __shared__ int bvh_lds[BRUTE ? 1 : kBvhStack * 256];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const float o[3] = {o0[i], o1[i], o2[i]}, d[3] = {d0[i], d1[i], d2[i]};
+    float t;
+    int best = quads_closest(S.quads, S.n_quads, o, d, mint, maxt, t);
+    if (S.n_tris > 0) {
+        if (BRUTE) {
+            mesh_brute(S.tris, S.n_tris, S.n_quads, o, d, mint, maxt, best, t);
+        } else {
+            LdsStack st{bvh_lds + threadIdx.x};
+            bvh_closest(S.nodes, S.tris, S.n_quads, o, d, mint, maxt, best, t, st);
+        }
+    }
+    float uv[2] = {0.0f, 0.0f}, rgb[3] = {0.0f, 0.0f, 0.0f};
+    if (best >= 0) {
+        if (best >= S.n_quads && !T.mesh_uv) {
+            // a mesh with neither mesh_uvs nor textures has no per-triangle table: the winner is looked
+            // for in the leaf-ordered array (this entry alone pays for that) and its test gives (u, v)
+            for (int k = 0; k < S.n_tris; ++k) {
+                if (S.tris[k].id != best - S.n_quads) continue;
+                float tt, u, v;
+                if (tri_intersect_uv(S.tris[k], o, d, &tt, &u, &v)) { uv[0] = u; uv[1] = v; }
+                break;
+            }
+        } else {
+            hit_uv(S.quads, S.n_quads, T.mesh_uv, best, o, d, uv);
+        }
+        const int qb = best >= S.n_quads ? S.hits[best - S.n_quads].bsdf : S.quads[best].bsdf;
+        hit_reflectance<true>(S.refl, T.tex, T.bsdf_tex, qb, uv, rgb);
+    }
+    prim[i] = best;
+    t_out[i] = t;
+    uv0[i] = uv[0]; uv1[i] = uv[1];
+    r[i] = rgb[0]; g[i] = rgb[1]; b[i] = rgb[2];
+}
+hipError_t launch_scene_texture(const SceneDev& S, const TexDev& T, int64_t nq, const float* const o[3],
+                                const float* const d[3], float mint, float maxt, int mode, int32_t* prim, float* t,
+                                float* const uv[2], float* const rgb[3], hipStream_t st) {
+    if (nq <= 0) return hipSuccess;
+    if (mode == 0)
+        hipLaunchKernelGGL(scene_texture_kernel<false>, grid_for(nq), dim3(256), 0, st, S, T, nq, o[0], o[1], o[2],
+                           d[0], d[1], d[2], mint, maxt, prim, t, uv[0], uv[1], rgb[0], rgb[1], rgb[2]);
+    else
+        hipLaunchKernelGGL(scene_texture_kernel<true>, grid_for(nq), dim3(256), 0, st, S, T, nq, o[0], o[1], o[2],
+                           d[0], d[1], d[2], mint, maxt, prim, t, uv[0], uv[1], rgb[0], rgb[1], rgb[2]);
     return hipGetLastError();
 }
 

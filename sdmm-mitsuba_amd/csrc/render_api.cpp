@@ -33,7 +33,7 @@ using namespace sdmm;
 struct sdmm_scene {
     int device = 0;
     SceneDev S{};
-    std::vector<void*> owned;   // the device blocks behind S, N.shade and S.env.texels (upload), freed by destroy
+    std::vector<void*> owned;   // the device blocks behind S, N.shade, T and S.env.texels (upload), freed by destroy
     float smin[3] = {0, 0, 0}, snorm = 1.0f, tmin[3] = {0, 0, 0}, tmax[3] = {0, 0, 0};
     // per-render buffers (grown)
     void* buf = nullptr;
@@ -43,6 +43,7 @@ struct sdmm_scene {
     PathsDev P{};
     QueryDev Q{};
     NormalsDev N{};   // (vertex normals: N.shade the scene's, the ns / ng planes in buf)
+    TexDev T{};       // (textures: T.tex, bsdf_tex, mesh_uv the scene's, the reflectance planes in buf)
     int64_t* dsum = nullptr;
     int32_t* dcount = nullptr;   // live guided queries of the current bounce
     int32_t* hcount = nullptr;   // (pinned host copy)
@@ -80,7 +81,7 @@ constexpr size_t align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 
 // The per-render arena of `cap` paths with `cv` vertex slots and `tb` bytes of
 // hipcub scratch: the path, query and vertex planes one after the other, each
-// on a 256-byte boundary.  base set: s->P, Q, N, dsum, temp and dcount point
+// on a 256-byte boundary.  base set: s->P, Q, N, T, dsum, temp and dcount point
 // into it; null: nothing is assigned.  Returns the arena's bytes either way.
 size_t layout_paths(sdmm_scene* s, char* base, int64_t cap, int cv, size_t tb) {
     size_t off = 0;
@@ -119,13 +120,16 @@ size_t layout_paths(sdmm_scene* s, char* base, int64_t cap, int cv, size_t tb) {
     take(Q.bdelta, u1);
     for (float** p : {&Q.bw0, &Q.bw1, &Q.bw2, &Q.bpdf}) take(*p, f);
     // the eta planes: only with a dielectric or a kind-5 / 6 BSDF; the ns / ng
-    // planes: only with vertex normals (null otherwise, as created)
+    // planes: only with vertex normals; the reflectance planes: only with a
+    // textured BSDF (null otherwise, as created)
     if (s->S.has_dielectric) {
         take(P.eta, f);
         take(Q.beta, f);
     }
     if (N.shade)
         for (float** p : {&N.nsx, &N.nsy, &N.nsz, &N.ngx, &N.ngy, &N.ngz}) take(*p, f);
+    if (s->T.bsdf_tex)
+        for (float** p : {&s->T.rr, &s->T.rg, &s->T.rb}) take(*p, f);
     return off;
 }
 
@@ -439,6 +443,78 @@ int build_host_scene(const sdmm_scene_desc* d, const char* who, int max_levels, 
     return SDMM_OK;
 }
 
+// The description's texture fields, validated (after every other check of the
+// description, the geometry's included): the textures as texture.h reads them
+// (texels: the caller's [h][w][3] arrays, in place), the per-triangle uv table
+// (with triangles and either mesh_uvs or a texture), and whether some BSDF
+// carries a texture.  0, or the error code (message set).
+struct HostTextures {
+    std::vector<TextureDev> tex;
+    std::vector<MeshUV> mesh_uv;
+    bool textured = false;
+};
+int prep_textures(const sdmm_scene_desc* d, const char* who, const HostScene& hs, HostTextures* ht) {
+    const std::string w(who);
+    if (d->mesh_uvs) {
+        if (d->n_triangles < 1) return fail(SDMM_E_INVALID, w + ": mesh_uvs without triangles");
+        for (int64_t i = 0; i < 2 * (int64_t)d->n_mesh_vertices; ++i)
+            if (!std::isfinite(d->mesh_uvs[i])) return fail(SDMM_E_INVALID, w + ": a non-finite mesh_uvs value");
+    }
+    if (d->n_textures < 0 || (d->n_textures > 0 && !d->textures))
+        return fail(SDMM_E_INVALID, w + ": n_textures < 0, or textures NULL with n_textures > 0");
+    if (d->bsdf_texture && d->n_textures < 1) return fail(SDMM_E_INVALID, w + ": bsdf_texture without textures");
+    int64_t total = 0;
+    for (int i = 0; i < d->n_textures; ++i) {
+        const sdmm_texture& t = d->textures[i];
+        if (t.width < 1 || t.height < 1) return fail(SDMM_E_INVALID, w + ": a texture's width or height < 1");
+        if (!t.pixels) return fail(SDMM_E_INVALID, w + ": a texture without pixels");
+        total += (int64_t)t.width * t.height;
+        if (total > kTexMaxTexels) return fail(SDMM_E_INVALID, w + ": textures of more than 2^26 texels in all");
+        if (t.filter != kTexBilinear && t.filter != kTexNearest)
+            return fail(SDMM_E_INVALID, w + ": a texture's filter outside 0..1");
+        if (t.wrap_u < kWrapRepeat || t.wrap_u > kWrapOne || t.wrap_v < kWrapRepeat || t.wrap_v > kWrapOne)
+            return fail(SDMM_E_INVALID, w + ": a texture's wrap_u or wrap_v outside 0..4");
+        for (int a = 0; a < 2; ++a) {
+            if (t.uv_scale[a] == 0.0f || !std::isfinite(t.uv_scale[a]))
+                return fail(SDMM_E_INVALID, w + ": a texture's uv_scale is 0 or not finite");
+            if (!std::isfinite(t.uv_offset[a])) return fail(SDMM_E_INVALID, w + ": a texture's uv_offset is not finite");
+        }
+        for (int64_t k = 0; k < 3 * (int64_t)t.width * t.height; ++k)
+            if (!(std::isfinite(t.pixels[k]) && t.pixels[k] >= 0.0f))
+                return fail(SDMM_E_INVALID, w + ": a non-finite or negative texel");
+        ht->tex.push_back(TextureDev{t.pixels, t.width, t.height, t.filter, t.wrap_u, t.wrap_v,
+                                     {t.uv_scale[0], t.uv_scale[1]}, {t.uv_offset[0], t.uv_offset[1]}});
+    }
+    if (d->bsdf_texture)
+        for (int b = 0; b < d->n_bsdfs; ++b) {
+            const int32_t ti = d->bsdf_texture[b];
+            if (ti < -1 || ti >= d->n_textures)
+                return fail(SDMM_E_INVALID, w + ": a bsdf_texture entry outside -1 .. n_textures - 1");
+            if (ti < 0) continue;
+            const float kind = bsdf_kind(d, b);
+            if (kind != (float)kBsdfDiffuse && kind != (float)kBsdfPlastic && kind != (float)kBsdfPhong)
+                return fail(SDMM_E_INVALID, w + ": bsdf_texture on a BSDF of kind 2, 4, 5 or 6 (only the reflectance "
+                                                "of kinds 0, 1 and 3 takes a texture)");
+            ht->textured = true;
+        }
+    if (hs.has_mesh && (d->mesh_uvs || d->n_textures > 0)) {
+        ht->mesh_uv.assign((size_t)d->n_triangles, MeshUV{});
+        for (const MeshTri& T : hs.mesh.tris) {
+            MeshUV& V = ht->mesh_uv[(size_t)T.id];
+            V.tri = T;
+            if (!d->mesh_uvs) continue;
+            const int32_t* ix = d->triangles + 3 * (int64_t)T.id;
+            for (int a = 0; a < 2; ++a) {
+                V.t0[a] = d->mesh_uvs[2 * (int64_t)ix[0] + a];
+                V.t1[a] = d->mesh_uvs[2 * (int64_t)ix[1] + a];
+                V.t2[a] = d->mesh_uvs[2 * (int64_t)ix[2] + a];
+            }
+            V.has_uv = 1;
+        }
+    }
+    return SDMM_OK;
+}
+
 // the closest hit of the ray (o, d) with t in (mint, maxt) among the quads and
 // the triangles (mode 0: the BVH, 1: the loop over all of them): the
 // primitive or -1, *t its distance (maxt without one)
@@ -538,6 +614,17 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
         for (size_t i = 0; i < env_texels.size(); ++i)
             env_texels[i] = EnvTexel{d->env_pixels[3 * i], d->env_pixels[3 * i + 1], d->env_pixels[3 * i + 2], 0.0f};
     }
+    // the textures: validated (the last checks), as RGBA texels (texture.h)
+    HostTextures ht;
+    rc = prep_textures(d, who, hs, &ht);
+    if (rc) return rc;
+    std::vector<std::vector<TexTexel>> tex_texels(ht.tex.size());
+    for (size_t i = 0; i < ht.tex.size(); ++i) {
+        const float* px = ht.tex[i].texels;
+        tex_texels[i].resize((size_t)ht.tex[i].w * (size_t)ht.tex[i].h);
+        for (size_t k = 0; k < tex_texels[i].size(); ++k)
+            tex_texels[i][k] = TexTexel{px[3 * k], px[3 * k + 1], px[3 * k + 2], 0.0f};
+    }
     sdmm_scene* s = new (std::nothrow) sdmm_scene();
     if (!s) return fail(SDMM_E_NOMEM, "out of host memory");
     s->device = device;
@@ -557,7 +644,7 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     }
     s->snorm = norm;
     // the device tables: an empty one (no mesh, no vertex normals, no map, no
-    // emitter, no bsdf_params, no model, no two-sided entry) stays null
+    // emitter, no bsdf_params, no model, no two-sided entry, no texture) stays null
     SceneDev& S = s->S;
     hipError_t e = hipSetDevice(device);
     const auto up = [&](const auto* host, size_t n, auto out, size_t alloc = 0) {
@@ -577,6 +664,14 @@ int sdmm_scene_create(const sdmm_scene_desc* d, int device, sdmm_scene** out) {
     up(lmod.data(), lmod.size(), &S.lmodel);
     up(lmod_nd.data(), lmod_nd.size(), &S.lmodel_nd);
     up(d->bsdf_twosided, hs.twosided ? nb : 0, &S.twosided);
+    for (size_t i = 0; i < ht.tex.size(); ++i) {
+        const TexTexel* tx = nullptr;
+        up(tex_texels[i].data(), tex_texels[i].size(), &tx);
+        ht.tex[i].texels = reinterpret_cast<const float*>(tx);
+    }
+    up(ht.tex.data(), ht.tex.size(), &s->T.tex);
+    up(d->bsdf_texture, ht.textured ? nb : 0, &s->T.bsdf_tex);
+    up(ht.mesh_uv.data(), ht.mesh_uv.size(), &s->T.mesh_uv);
     if (e != hipSuccess) {
         sdmm_scene_destroy(s);
         return fail(SDMM_E_HIP, w + ": " + hipGetErrorString(e));
@@ -860,6 +955,48 @@ int sdmm_scene_shading_host(const sdmm_scene_desc* desc, int64_t nq, const float
     return SDMM_OK;
 }
 
+int sdmm_scene_texture(const sdmm_scene* s, int64_t nq, const float* const o[3], const float* const d[3], float mint,
+                       float maxt, int mode, int32_t* prim, float* t, float* const uv[2], float* const rgb[3],
+                       void* hip_stream) {
+    if (!s || nq < 0 || (mode != 0 && mode != 1))
+        return fail(SDMM_E_INVALID, "sdmm_scene_texture: invalid argument (mode 0 or 1)");
+    if (nq == 0) return SDMM_OK;
+    if (!o || !o[0] || !o[1] || !o[2] || !d || !d[0] || !d[1] || !d[2] || !prim || !t || !uv || !uv[0] || !uv[1] ||
+        !rgb || !rgb[0] || !rgb[1] || !rgb[2])
+        return fail(SDMM_E_INVALID, "sdmm_scene_texture: NULL plane");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(launch_scene_texture(s->S, s->T, nq, o, d, mint, maxt, mode, prim, t, uv, rgb, (hipStream_t)hip_stream));
+    return SDMM_OK;
+}
+
+int sdmm_scene_texture_host(const sdmm_scene_desc* desc, int64_t nq, const float* o, const float* d, float mint,
+                            float maxt, int mode, int32_t* prim, float* t, float* uv, float* rgb) {
+    if (!desc || nq < 0 || (mode != 0 && mode != 1) || (nq > 0 && (!o || !d || !prim || !t || !uv || !rgb)))
+        return fail(SDMM_E_INVALID, "sdmm_scene_texture_host: invalid argument (mode 0 or 1)");
+    HostScene hs;
+    if (const int rc = build_host_scene(desc, "sdmm_scene_texture_host", 0, &hs)) return rc;
+    HostTextures ht;
+    if (const int rc = prep_textures(desc, "sdmm_scene_texture_host", hs, &ht)) return rc;
+    // (the uv table also for a mesh with neither mesh_uvs nor textures: the test's own u, v)
+    if (hs.has_mesh && ht.mesh_uv.empty()) {
+        ht.mesh_uv.assign(hs.mesh.tris.size(), MeshUV{});
+        for (const MeshTri& T : hs.mesh.tris) ht.mesh_uv[(size_t)T.id].tri = T;
+    }
+    const int nquads = (int)hs.quads.size();
+    const DeviceFloatEnv env;
+    for (int64_t i = 0; i < nq; ++i) {
+        prim[i] = closest(hs, mode, o + 3 * i, d + 3 * i, mint, maxt, t + i);
+        uv[2 * i] = uv[2 * i + 1] = 0.0f;
+        for (int a = 0; a < 3; ++a) rgb[3 * i + a] = 0.0f;
+        if (prim[i] < 0) continue;
+        hit_uv(hs.quads.data(), nquads, ht.mesh_uv.data(), prim[i], o + 3 * i, d + 3 * i, uv + 2 * i);
+        const int qb = prim[i] >= nquads ? hs.mesh.hits[(size_t)(prim[i] - nquads)].bsdf : hs.quads[(size_t)prim[i]].bsdf;
+        hit_reflectance<false>(desc->reflectance, ht.tex.data(), ht.textured ? desc->bsdf_texture : nullptr, qb,
+                               uv + 2 * i, rgb + 3 * i);
+    }
+    return SDMM_OK;
+}
+
 int sdmm_env_eval(const sdmm_scene* s, int64_t nq, const float* const d[3], float* const rgb[3], void* hip_stream) {
     if (!s || nq < 0) return fail(SDMM_E_INVALID, "sdmm_env_eval: invalid argument");
     if (nq == 0) return SDMM_OK;
@@ -945,7 +1082,7 @@ int sdmm_li_render(sdmm_scene* s, sdmm_stree* t, const sdmm_mix* const* node_mix
         if (r) return r;
     }
     const int64_t path0 = p->pixel_begin * p->spp;
-    HIP_TRY(launch_li_camera(s->S, s->P, s->N, path0, p->spp, p->seed, st));
+    HIP_TRY(launch_li_camera(s->S, s->P, s->N, s->T, path0, p->spp, p->seed, st));
     // bounces: rRec.depth 1 .. maxDepth - 1 scatter (:649, :684); unbounded
     // paths stop at the vertex slots
     const int bounces = p->max_depth > 0 ? p->max_depth - 1 : V;
@@ -962,7 +1099,7 @@ int sdmm_li_render(sdmm_scene* s, sdmm_stree* t, const sdmm_mix* const* node_mix
         for (int b = 0; b < bounces; ++b) s->hfb[b] = 0;
     const float h = p->bsdf_fraction;
     for (int b = 0; b < bounces; ++b) {
-        HIP_TRY(launch_li_query(s->S, s->P, s->Q, s->N, path0, b, p->max_depth > 0 ? p->max_depth : INT32_MAX, p->guided,
+        HIP_TRY(launch_li_query(s->S, s->P, s->Q, s->N, s->T, path0, b, p->max_depth > 0 ? p->max_depth : INT32_MAX, p->guided,
                                 h, p->seed, st));
         if (p->guided) {
             // only the live paths query the guide: compact them (the order of
@@ -998,7 +1135,7 @@ int sdmm_li_render(sdmm_scene* s, sdmm_stree* t, const sdmm_mix* const* node_mix
             }
             guided_queries += nlive;
         }
-        HIP_TRY(launch_li_shade(s->S, s->P, s->Q, s->N, path0, b, p->rr_depth, h, p->seed, product && p->guided, st));
+        HIP_TRY(launch_li_shade(s->S, s->P, s->Q, s->N, s->T, path0, b, p->rr_depth, h, p->seed, product && p->guided, st));
     }
     HIP_TRY(launch_li_film(s->P, p->pixel_begin, npix, p->spp, npix_all, image, image_sqr, st));
     if (vout) {

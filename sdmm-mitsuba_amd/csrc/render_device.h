@@ -6,6 +6,7 @@
 
 #include "mesh_bvh.h"
 #include "envmap.h"
+#include "texture.h"
 
 namespace sdmm {
 
@@ -124,6 +125,53 @@ __host__ __device__ __forceinline__ void hit_normals(const SceneDev& S, const Me
         return;
     }
     for (int a = 0; a < 3; ++a) ns[a] = ng[a] = S.quads[q].n[a];
+}
+
+// What only the TEX variants of the Li kernels read (a scene whose BSDFs carry
+// bitmap textures, texture.h): a record of its own, passed after every other
+// kernel argument (after NormalsDev where both are), as NormalsDev is and for
+// the same reason.
+struct TexDev {
+    const TextureDev* tex;       // the scene's textures (texels: TexTexel on the device)
+    const int32_t* bsdf_tex;     // per BSDF: its reflectance's texture, -1 none; null: no BSDF is textured
+    const MeshUV* mesh_uv;       // by triangle index; null without a mesh (or with neither mesh_uvs nor textures)
+    // the current hit's effective reflectance (the texture's value at the
+    // hit's uv, or the BSDF's row), one plane a channel: written by the kernel
+    // that traced the ray (camera, shade), read by the next bounce's kernels;
+    // null without textures
+    float *rr, *rg, *rb;
+};
+
+// the effective reflectance of BSDF b at a hit with texture coordinates uv:
+// its texture's value, or its row
+template <bool RGBA>
+__host__ __device__ __forceinline__ void hit_reflectance(const float* refl, const TextureDev* tex,
+                                                         const int32_t* bsdf_tex, int b, const float uv[2],
+                                                         float rgb[3]) {
+    const int ti = bsdf_tex ? bsdf_tex[b] : -1;
+    if (ti >= 0) {
+        tex_eval<RGBA>(tex[ti], uv, rgb);
+        return;
+    }
+    for (int ch = 0; ch < 3; ++ch) rgb[ch] = refl[3 * b + ch];
+}
+
+// hit_normals and hit_uv (texture.h) of one hit together: on a triangle with
+// vertex normals the test on the winner runs once and serves both
+__host__ __device__ __forceinline__ void hit_normals_uv(const SceneDev& S, const MeshShade* shade,
+                                                        const MeshUV* mesh_uv, int q, const float o[3],
+                                                        const float d[3], float ns[3], float ng[3], float uv[2]) {
+    if (q >= S.n_quads && shade) {
+        const int ti = q - S.n_quads;
+        float t, u = 0.0f, v = 0.0f;
+        const bool hit = tri_intersect_uv(shade[ti].tri, o, d, &t, &u, &v);
+        shading_normals_at(shade[ti], S.hits[ti].n, hit, u, v, ns, ng);
+        uv[0] = uv[1] = 0.0f;
+        if (hit) tri_uv(mesh_uv[ti], u, v, uv);
+        return;
+    }
+    hit_normals(S, nullptr, q, o, d, ns, ng);
+    hit_uv(S.quads, S.n_quads, mesh_uv, q, o, d, uv);
 }
 
 // a hit from behind (cos_i = wi . n < 0) on a two-sided BSDF: the bounce runs

@@ -9,12 +9,15 @@
 namespace sdmm {
 
 // N: the vertex normals' record (N.shade null: none, the kernels' other variants run and read nothing of it)
-hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, const NormalsDev& N, int64_t path0, int spp,
-                            uint64_t seed, hipStream_t st);
-hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N, int64_t path0,
-                           int bounce, int max_depth, int guided, float h, uint64_t seed, hipStream_t st);
-hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N, int64_t path0,
-                           int bounce, int rr_depth, float h, uint64_t seed, int product, hipStream_t st);
+// T: the textures' record (T.bsdf_tex null: no BSDF is textured, likewise)
+hipError_t launch_li_camera(const SceneDev& S, const PathsDev& P, const NormalsDev& N, const TexDev& T, int64_t path0,
+                            int spp, uint64_t seed, hipStream_t st);
+hipError_t launch_li_query(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N,
+                           const TexDev& T, int64_t path0, int bounce, int max_depth, int guided, float h,
+                           uint64_t seed, hipStream_t st);
+hipError_t launch_li_shade(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N,
+                           const TexDev& T, int64_t path0, int bounce, int rr_depth, float h, uint64_t seed,
+                           int product, hipStream_t st);
 size_t li_select_temp_bytes(int64_t n);
 hipError_t launch_li_compact(const SceneDev& S, const PathsDev& P, const QueryDev& Q, const NormalsDev& N, int64_t n,
                              int32_t* count_dev, void* temp, size_t temp_bytes, int product, hipStream_t st);
@@ -25,6 +28,9 @@ hipError_t launch_scene_intersect(const SceneDev& S, int64_t nq, const float* co
 hipError_t launch_scene_shading(const SceneDev& S, const MeshShade* shade, int64_t nq, const float* const o[3],
                                 const float* const d[3], float mint, float maxt, int mode, int32_t* prim, float* t,
                                 float* const ns[3], float* const ng[3], hipStream_t st);
+hipError_t launch_scene_texture(const SceneDev& S, const TexDev& T, int64_t nq, const float* const o[3],
+                                const float* const d[3], float mint, float maxt, int mode, int32_t* prim, float* t,
+                                float* const uv[2], float* const rgb[3], hipStream_t st);
 hipError_t launch_env_eval(const SceneDev& S, int64_t nq, const float* const d[3], float* const rgb[3],
                            hipStream_t st);
 hipError_t launch_roughdielectric(const float* bp, const float st[3], int64_t nq, const float* const wi[3],

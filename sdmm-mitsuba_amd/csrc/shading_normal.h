@@ -64,4 +64,30 @@ SDMM_MESH_HD void shading_normals(const MeshShade& V, const float face[3], const
         for (int a = 0; a < 3; ++a) ng[a] = -ng[a];
 }
 
+// The same from the test's outcome (hit; u, v), for a caller that ran the test
+// itself because it needs the barycentrics for the hit's uv as well
+// (texture.h): the test on the winner then runs once for both.  (Stated twice
+// rather than called from shading_normals: the kernels that call that one keep
+// their code.)
+SDMM_MESH_HD void shading_normals_at(const MeshShade& V, const float face[3], bool hit, float u, float v,
+                                     float ns[3], float ng[3]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    for (int a = 0; a < 3; ++a) ns[a] = ng[a] = face[a];
+    if (!hit) return;
+    const float b0 = 1.0f - u - v;
+    float s[3];
+    for (int a = 0; a < 3; ++a) s[a] = V.n0[a] * b0 + V.n1[a] * u + V.n2[a] * v;
+    const float len = __builtin_sqrtf(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+    if (!(len > 0.0f) || len == __builtin_inff()) return;
+    const float sg = V.flip ? -1.0f : 1.0f;
+    for (int a = 0; a < 3; ++a) {
+        ns[a] = sg * (s[a] / len);
+        ng[a] = sg * face[a];
+    }
+    if (ng[0] * ns[0] + ng[1] * ns[1] + ng[2] * ns[2] < 0.0f)
+        for (int a = 0; a < 3; ++a) ng[a] = -ng[a];
+}
+
 }  // namespace sdmm

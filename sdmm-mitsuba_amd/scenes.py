@@ -176,6 +176,40 @@ def phong_params(diffuse_rgb, specular_rgb=(0.2, 0.2, 0.2), exponent=30.0):
     return np.array([3.0, *sp, exponent, ssw, 0.0, 0.0], f32), d
 
 
+def checker_texture(w, h, a=(0.8, 0.8, 0.8), b=(0.1, 0.1, 0.1), **fields):
+    """A texture (a dict for the description's "textures") of w x h texels,
+    texel (x, y) colour a where x + y is even and b where it is odd; nearest
+    filter, repeat wrap.  fields: further entries ("filter", "wrap_u",
+    "wrap_v", "uv_scale", "uv_offset") or overrides."""
+    y, x = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    px = np.where(((x + y) % 2 == 0)[..., None], np.asarray(a, np.float32), np.asarray(b, np.float32))
+    return {"pixels": np.ascontiguousarray(px, np.float32), "filter": "nearest", "wrap_u": "repeat",
+            "wrap_v": "repeat", **fields}
+
+
+def ramp_texture(w, h, **fields):
+    """A texture of w x h texels whose red grows with x, green with y (both
+    from 0.1 to 0.9 over the texel centres) and whose blue is 0.5; bilinear
+    filter, clamp wrap.  fields: as checker_texture's."""
+    y, x = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    r = 0.1 + 0.8 * (x / max(1, w - 1))
+    g = 0.1 + 0.8 * (y / max(1, h - 1))
+    px = np.stack([r, g, np.full_like(r, 0.5)], -1)
+    return {"pixels": np.ascontiguousarray(px, np.float32), "filter": "bilinear", "wrap_u": "clamp",
+            "wrap_v": "clamp", **fields}
+
+
+def texture_mean(texture):
+    """The texture's average colour (Texture::getAverage of a bitmap: the mean
+    over its texels), float32 [3]: what Phong::configure() and
+    SmoothPlastic::configure() take for the diffuse part of their specular
+    sampling weight and energy scaling (phong.cpp:146-148, plastic.cpp:
+    159-175) -- pass it as the diffuse_rgb of phong_params / plastic_params
+    for a BSDF whose reflectance is this texture; the constant bsdf_params
+    stay the caller's."""
+    return np.asarray(texture["pixels"], np.float64).reshape(-1, 3).mean(0).astype(np.float32)
+
+
 def dielectric_params(specular_rgb=(1.0, 1.0, 1.0), transmittance_rgb=(1.0, 1.0, 1.0), int_ior=1.5046,
                       ext_ior=1.000277, alpha=0.1):
     """(the 8 bsdf_params floats of a rough dielectric, its
@@ -259,7 +293,7 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
                 phong_learned=LEARNED_PHONG, phong_specular=(0.4, 0.4, 0.4), phong_exponent=30.0, dielectric=(),
                 dielectric_learned=LEARNED_DIELECTRIC, dielectric_alpha=0.1, dielectric_ior=(1.5046, 1.000277),
                 dielectric_specular=(1.0, 1.0, 1.0), dielectric_transmittance=(1.0, 1.0, 1.0), dielectric_lift=0.0,
-                mesh=(), glass=(), mirror=(), mirror_eta_k=(1.2, 7.0), twosided=()):
+                mesh=(), glass=(), mirror=(), mirror_eta_k=(1.2, 7.0), twosided=(), textured=False):
     """sdmm_scene_desc fields for the Cornell Box (numpy arrays).  plastic:
     names of BSDFs (e.g. "TallBox", "ShortBox", "Floor") rendered as smooth
     plastic over their diffuse reflectance (a delta specular lobe beside a
@@ -290,8 +324,20 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
     learned model: their bounces are delta only.
     twosided: names wrapped in the single-child `twosided` adapter (the
     description's bsdf_twosided; not a `dielectric` or `glass` name, which
-    transmit).  The box is closed, so no path meets such a BSDF from behind."""
+    transmit).  The box is closed, so no path meets such a BSDF from behind.
+    textured: a checker (8 x 8 texels of the floor's colour and a dark gray,
+    nearest, tiled twice each way) on the floor's reflectance and a ramp (16 x
+    16, bilinear, clamped) on the back wall's, which becomes a Phong BSDF
+    (phong_specular / phong_exponent, its sampling weight from the ramp's
+    mean, the shipped learned SDMM5) -- the description's textures and
+    bsdf_texture; quads carry their own (a, b) as uv.  "Floor" and "BackWall"
+    then take no other material."""
     names = list(_BSDFS)
+    if textured:
+        if {"Floor", "BackWall"} & (set(plastic) | set(conductor) | set(phong) | set(dielectric) | set(glass) |
+                                    set(mirror)):
+            raise ValueError("textured: Floor and BackWall take no other material")
+        phong = tuple(phong) + ("BackWall",)
     quads, bsdf, flip, emitter = [], [], [], []
     mesh_quads, mesh_bsdf = [], []
     if set(mesh) - {name for _, name in _CUBES}:
@@ -332,6 +378,9 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
                 bp[i] = conductor_params(tuple(min(1.0, 1.25 * c) for c in _BSDFS[nm]), alpha=alpha)
             elif nm in phong:
                 bp[i], refl[nm] = phong_params(_BSDFS[nm], phong_specular, phong_exponent)
+                if textured and nm == "BackWall":
+                    # (the sampling weight from the texture's mean; the row itself is replaced at every hit)
+                    bp[i], refl[nm] = phong_params(texture_mean(ramp_texture(16, 16)), phong_specular, phong_exponent)
             elif nm in dielectric:
                 bp[i], refl[nm] = dielectric_params(dielectric_specular, dielectric_transmittance, *dielectric_ior,
                                                     alpha=dielectric_alpha)
@@ -356,6 +405,10 @@ def cornell_box(width=640, height=360, plastic=(), conductor=(), alpha=0.2, lear
         if bad:
             raise ValueError(f"twosided: unknown or transmitting BSDFs {sorted(bad)}")
         extra["bsdf_twosided"] = np.asarray([int(nm in twosided) for nm in names], np.int32)
+    if textured:
+        extra["textures"] = [checker_texture(8, 8, _BSDFS["Floor"], (0.15, 0.15, 0.15), uv_scale=2.0),
+                             ramp_texture(16, 16)]
+        extra["bsdf_texture"] = np.asarray([{"Floor": 0, "BackWall": 1}.get(nm, -1) for nm in names], np.int32)
     return {**extra,
         "quads": np.asarray(quads, np.float32).reshape(-1),
         "flip_normals": np.asarray(flip, np.int32),
@@ -401,14 +454,17 @@ def vertex_normals(vertices, triangles):
     return N.astype(np.float32)
 
 
-def torus_mesh(nu, nv, R=1.0, r=0.4, to_world=None, normals=False):
+def torus_mesh(nu, nv, R=1.0, r=0.4, to_world=None, normals=False, uvs=False):
     """A torus about the y axis (centre circle of radius R in the xz plane,
     tube radius r) as nu x nv quads of two triangles: (vertices [nu * nv, 3]
     float32, triangles [2 * nu * nv, 3] int32), counter-clockwise seen from
     outside.  to_world: a 3x4 or 4x4 matrix applied to the vertices.
     normals: also the analytic unit outward normals at the vertices (float32
     [nu * nv, 3], third of the tuple), through to_world's inverse transpose
-    and normalised again."""
+    and normalised again.  uvs: also the vertices' texture coordinates (i / nu,
+    j / nv) (float32 [nu * nv, 2], last of the tuple) -- the ring closes on
+    shared vertices, so the last cells along each direction run back from
+    (n - 1) / n to 0."""
     u = 2.0 * np.pi * np.arange(nu) / nu
     v = 2.0 * np.pi * np.arange(nv) / nv
     uu, vv = np.meshgrid(u, v, indexing="ij")
@@ -429,9 +485,12 @@ def torus_mesh(nu, nv, R=1.0, r=0.4, to_world=None, normals=False):
     tris = np.concatenate([np.stack([a, d, c], -1), np.stack([a, c, b], -1)], 1).reshape(-1, 3)
     if to_world is not None and np.linalg.det(M[:, :3]) < 0:
         tris = tris[:, ::-1]
+    out = (P.astype(np.float32), np.ascontiguousarray(tris, np.int32))
     if normals:
-        return P.astype(np.float32), np.ascontiguousarray(tris, np.int32), Nn.astype(np.float32)
-    return P.astype(np.float32), np.ascontiguousarray(tris, np.int32)
+        out += (Nn.astype(np.float32),)
+    if uvs:
+        out += (np.stack([i / nu, j / nv], -1).reshape(-1, 2).astype(np.float32),)
+    return out
 
 
 def convex_mesh():
@@ -613,13 +672,14 @@ def torus_scene(width=640, height=360, nu=96, nv=48, glass=True, environment=Non
 
 
 def sheet_mesh(nx, nz, x=(-1.8, 1.8), z=(1.4, -2.6), y0=1.6, amplitude=0.45, waves=1.25, phase=np.pi,
-               normals=False):
+               normals=False, uvs=False):
     """An open sheet: the height field y = y0 + amplitude sin(2 pi waves s +
     phase) over x[0]..x[1] and, along s in [0, 1], z[0]..z[1], as nx x nz
     cells of two triangles with the face normals on the +y side: (vertices
     [(nx + 1)(nz + 1), 3] float32, triangles [2 nx nz, 3] int32).  normals:
     also the height field's analytic unit normals at the vertices, on the +y
-    side (float32, third of the tuple)."""
+    side (float32, third of the tuple).  uvs: also the vertices' texture
+    coordinates (a, s), both over [0, 1] (float32 [., 2], last of the tuple)."""
     a = np.linspace(0.0, 1.0, nx + 1)
     s = np.linspace(0.0, 1.0, nz + 1)
     aa, ss = np.meshgrid(a, s, indexing="ij")
@@ -637,15 +697,19 @@ def sheet_mesh(nx, nz, x=(-1.8, 1.8), z=(1.4, -2.6), y0=1.6, amplitude=0.45, wav
         dyds = amplitude * 2.0 * np.pi * waves * np.cos(2.0 * np.pi * waves * ss + phase)
         Nn = np.stack([np.zeros_like(ss), np.ones_like(ss), -dyds / (z[1] - z[0])], -1).reshape(-1, 3)
         Nn /= np.linalg.norm(Nn, axis=1, keepdims=True)
-        return P.astype(np.float32), np.ascontiguousarray(tris, np.int32), Nn.astype(np.float32)
-    return P.astype(np.float32), np.ascontiguousarray(tris, np.int32)
+    out = (P.astype(np.float32), np.ascontiguousarray(tris, np.int32))
+    if normals:
+        out += (Nn.astype(np.float32),)
+    if uvs:
+        out += (np.stack([aa, ss], -1).reshape(-1, 2).astype(np.float32),)
+    return out
 
 
 SHEET_MATERIALS = ("diffuse", "plastic", "conductor", "phong", "mirror")   # kinds 0, 1, 2, 3, 6
 
 
 def sheet_scene(width=640, height=360, nx=16, nz=48, material="diffuse", twosided=True, environment=None,
-                reflectance=(0.7, 0.6, 0.4), learned=True, patch=False, smooth_normals=False):
+                reflectance=(0.7, 0.6, 0.4), learned=True, patch=False, smooth_normals=False, texture=None):
     """An open surface for the `twosided` adapter: torus_scene's lit room (or,
     with environment=, its open floor under that sky) holding a sheet --
     sheet_mesh(nx, nz), a sine wave hanging at the camera's height and running
@@ -661,9 +725,16 @@ def sheet_scene(width=640, height=360, nx=16, nz=48, material="diffuse", twoside
     lying face up above the sheet and the camera: what reaches it from below
     meets its back, and in the open scene (environment=) nothing lies above
     it, so every hit on it is one from behind.  smooth_normals: the sheet
-    carries its analytic vertex normals (mesh_normals)."""
+    carries its analytic vertex normals (mesh_normals).  texture: a texture
+    (checker_texture / ramp_texture) on the sheet's reflectance, looked up at
+    the sheet's own uvs (mesh_uvs) -- a diffuse, plastic or Phong sheet, whose
+    sampling weight then comes from the texture's mean."""
     if material not in SHEET_MATERIALS:
         raise ValueError(f"material: one of {SHEET_MATERIALS}")
+    if texture is not None:
+        if material not in ("diffuse", "plastic", "phong"):
+            raise ValueError("texture: on a diffuse, plastic or phong sheet")
+        reflectance = tuple(float(c) for c in texture_mean(texture))
     names = ["Room", "Floor", "Sheet", "Light"] + (["Patch"] if patch else [])
     refl = {"Room": (0.6, 0.6, 0.6), "Floor": (0.5, 0.5, 0.5), "Sheet": tuple(reflectance), "Light": (0.0, 0.0, 0.0),
             "Patch": (0.0, 0.0, 0.0)}
@@ -711,9 +782,13 @@ def sheet_scene(width=640, height=360, nx=16, nz=48, material="diffuse", twoside
         extra["bsdf_twosided"] = np.asarray([int(nm in ("Sheet", "Patch")) for nm in names], np.int32)
     if environment is not None:
         extra.update(environment)
-    verts, tris, vnrm = sheet_mesh(nx, nz, normals=True)
+    verts, tris, vnrm, vuv = sheet_mesh(nx, nz, normals=True, uvs=True)
     if smooth_normals:
         extra["mesh_normals"] = vnrm.reshape(-1)
+    if texture is not None:
+        extra["mesh_uvs"] = vuv.reshape(-1)
+        extra["textures"] = [texture]
+        extra["bsdf_texture"] = np.asarray([0 if nm == "Sheet" else -1 for nm in names], np.int32)
     return {**extra,
         "quads": np.asarray(quads, np.float32).reshape(-1),
         "bsdf": np.asarray(bsdf, np.int32),
@@ -749,7 +824,9 @@ def mirror_z(desc, keep=()):
     and a triangle listed in `keep` gets its flag toggled: ns = -mirror(ns),
     met from the other side.  (Where the interpolated normal vanishes the
     library falls back to the face normal with the flag applied, which this
-    rule leaves negated.)  Mirroring twice gives the description back."""
+    rule leaves negated.)  mesh_uvs, textures and bsdf_texture are carried as
+    they are: a quad's (a, b) and a triangle's (u, v) are the mirrored
+    primitive's bit for bit (a zero may change its sign).  Mirroring twice gives the description back."""
     out = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in desc.items()}
     keep = set(int(k) for k in keep)
     nq = 0

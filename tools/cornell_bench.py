@@ -17,6 +17,9 @@
 --smooth-normals   with --torus: the torus carries its analytic vertex normals
                    (scenes.torus_scene(smooth_normals=True)): the Li kernels'
                    NRM variants run
+--textured         the Cornell box with scenes.cornell_box(textured=True): a
+                   checker on the floor, a ramp on a Phong back wall -- the Li
+                   kernels' TEX variants run (not with --torus)
 --env-eval N       time sdmm_env_eval on 2^N random directions against a
                    1024x512 map (device time per launch from events); with
                    --repeat 0 nothing else runs
@@ -54,6 +57,7 @@ if __name__ == "__main__":
     ap.add_argument("--intersect", type=int, default=0, help="--torus: time Scene.intersect on 2^N rays")
     ap.add_argument("--env", action="store_true", help="--torus: the open scene under a sky environment map")
     ap.add_argument("--smooth-normals", action="store_true", help="--torus: vertex normals on the torus")
+    ap.add_argument("--textured", action="store_true", help="bitmap textures on the floor and the back wall")
     ap.add_argument("--env-eval", type=int, default=0, help="time Scene.env_eval on 2^N directions, 1024x512 map")
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--summary", action="store_true", help="one line per run, no per-iteration lines")
@@ -67,6 +71,11 @@ if __name__ == "__main__":
         scenes = importlib.import_module("sdmm_mitsuba_amd.scenes")
         scenes.cornell_box = functools.partial(scenes.cornell_box, dielectric=tuple(a.dielectric),
                                                dielectric_lift=0.02)
+    if a.textured:
+        if a.torus or "Floor" in a.glossy + a.phong + a.dielectric or "BackWall" in a.glossy + a.phong + a.dielectric:
+            ap.error("--textured: the Cornell box, Floor and BackWall taking no other material")
+        scenes = importlib.import_module("sdmm_mitsuba_amd.scenes")
+        scenes.cornell_box = functools.partial(scenes.cornell_box, textured=True)
     if a.env and not a.torus:
         ap.error("--env goes with --torus")
     if a.smooth_normals and not a.torus:
@@ -171,6 +180,8 @@ if __name__ == "__main__":
                 out["workload"] += " (Phong " + "/".join(a.phong) + ")"
             if a.dielectric:
                 out["workload"] += " (rough dielectric " + "/".join(a.dielectric) + ")"
+            if a.textured:
+                out["workload"] += " (textured floor and back wall)"
             print(json.dumps({k: v for k, v in out.items() if k != "iterations"}), flush=True)
             if not a.summary:
                 for it in out["iterations"]:
